@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: distillation iterations/sec (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when --dump-outputs
+is given and prints the result line.  --full adds everything else the benchmark measures or checks, after the
+timed steps: the instrumented roofline iteration, the self-check against an f32-mode engine (with the bf16x2
+parity timing), the CPU baseline and the configs[3] / configs[4] child runs (`other_workloads`).
 
 One "step" = one outer distillation iteration on one expert trajectory (reference
 distill.py:466-613 minus eval/logging/student rebuild): syn_steps unrolled student steps
@@ -34,6 +39,7 @@ WORKLOADS = {
     "c5": ("vit_b16", 100, 8, 224, 512),      # configs[4] per GPU: ViT-B/16 image encoder + 512-d CLIP text embeddings
     "tiny": ("nfnet_tiny", 4, 2, 64, 32),     # plumbing
 }
+DUMP_SAMPLE = 1 << 20       # --dump-outputs: larger outputs are written as this many seeded sample elements
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA (guides/MI355X_MICROARCH.md)
 PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
@@ -111,6 +117,25 @@ def cpu_baseline(workload, seconds_budget=30.0):
     return out
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  An array of more than DUMP_SAMPLE elements is
+    written as DIR/<name>_sample.npy: the elements at DUMP_SAMPLE fixed positions (seeded, sorted, drawn with
+    replacement), the same positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(1234)
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 * 10**6, "--dump-outputs wrote %d bytes" % total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -139,9 +164,22 @@ def main():
                          "while this iteration runs (BASELINE configs[3]: expert buffer streaming); 'hbm' = copied out "
                          "of a resident [E, 2, P] pool on the copy stream")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default C2 run only: skip the short configs[3] / configs[4] child runs reported under "
+                    help="--full C2 run only: skip the short configs[3] / configs[4] child runs reported under "
                          "`other_workloads`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline iteration, the self-check, the CPU baseline "
+                         "and the other workloads (each can still be left out with its --no-* option); without "
+                         "--full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, the outer gradients and the updated "
+                         "synthetic set) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_launches and (not args.full or args.no_roofline):
+        ap.error("--dump-launches needs --full (the launches are those of the roofline iteration)")
+    if not args.full:
+        args.no_roofline = args.no_selfcheck = args.no_cpu_baseline = args.no_other_workloads = True
 
     # A stray MDD_* variable must never shape the headline number: the product library ignores all of
     # them (work-skipping switches exist only in -DMDD_DEBUG_SWITCHES experiment builds, and
@@ -207,8 +245,15 @@ def main():
     # (lr * K * |g0|), as oracle/gen_golden.py does -- so the normalised matching loss (distill.py:596-597)
     # and every outer gradient depend O(1) on what the conv kernels compute (a 1e-3 displacement swamps the
     # student's move: grand_loss = 2 whatever the kernels do).
+    # sigma is rounded to 4 significant digits and the noise drawn again from the re-seeded generator: the gradient
+    # norms sigma comes from carry the fp32-atomic summation order (~1e-7), and the benchmark's inputs must be
+    # identical from run to run (--dump-outputs compares builds output for output).
     from multimodal_dataset_distillation_amd.networks import student_move_normalised_targets
-    tgi, tgt, sig_i, sig_t = student_move_normalised_targets(eng, th0i, th0t, image_syn, text_syn, lr, K, gt)
+    _, _, sig_i, sig_t = student_move_normalised_targets(eng, th0i, th0t, image_syn, text_syn, lr, K, gt)
+    sig_i, sig_t = float("%.4g" % sig_i), float("%.4g" % sig_t)
+    gt.manual_seed(200 + rank)
+    tgi = th0i + sig_i * torch.randn(th0i.shape, device=dev, generator=gt)
+    tgt = th0t + sig_t * torch.randn(th0t.shape, device=dev, generator=gt)
     # ---- expert snapshot source (distill.py:450-476).  'host' / 'hbm': a pool of E pairs [theta_start | theta_target]
     # (image and text networks back to back); every iteration uses pair (i mod E) out of a two-deep device buffer that
     # the copy stream fills one iteration ahead -- the timed loop then contains the reference's per-iteration expert
@@ -315,6 +360,12 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     losses = out["losses"].cpu().tolist()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the losses [grand, img, txt, contrastive x K],
+        # the outer gradients, and the synthetic set after the three SGD-momentum updates
+        dump_outputs(args.dump_outputs, dict(losses=out["losses"], grad_image_syn=out["image_syn"],
+                                             grad_text_syn=out["text_syn"], grad_lr=out["lr"], image_syn=image_syn,
+                                             text_syn=text_syn, lr=lr))
     # gradient norms of the last timed step (of THIS rank's reduced buffer) -- what the kernels produced
     gnorm = dict(grad_image_syn=float(out["image_syn"].norm()), grad_text_syn=float(out["text_syn"].norm()),
                  grad_lr=[float(v) for v in out["lr"].tolist()])
@@ -541,8 +592,8 @@ def main():
         others = {}
         for name, extra in (("c4", ["--keep-steps", "0", "--steps", "1", "--warmup", "1", "--expert-source", "host"]),
                             ("c5", ["--steps", "4", "--warmup", "1"])):
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--no-cpu-baseline", "--no-roofline",
-                   "--no-other-workloads"] + extra
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--full", "--no-cpu-baseline",
+                   "--no-roofline", "--no-other-workloads"] + extra
             t1 = time.time()
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)

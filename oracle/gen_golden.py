@@ -85,6 +85,18 @@ def f32(t):
     return t.detach().cpu().numpy().astype(np.float32)
 
 
+FINGERPRINT_STRIDE = 97
+
+
+def fingerprint(rec, key, t):
+    """A flat parameter vector the tests regenerate from the golden's seeds instead of loading it (stored in full,
+    the fixture would exceed the repository's 1 MiB file limit): every 97th element and the float64 sum, which
+    tests/golden_inputs.py checks the regenerated vector against."""
+    flat = t.detach().reshape(-1)
+    rec[key + "_sample"] = f32(flat[::FINGERPRINT_STRIDE])
+    rec[key + "_sum"] = np.float64(flat.double().sum().item())
+
+
 def gen_text_only(ReparamModule, RefHead, path):
     """Pinned 100% by reference code: ReparamModule(ProjectionHead) + the loop, image features
     held constant.  Covers SURVEY 8a rows a4,a6,a7,a8(txt),a9,a10,a11(txt)."""
@@ -131,11 +143,14 @@ def gen_text_only(ReparamModule, RefHead, path):
         tp.append(tp[-1] - lr_txt * tg)
     assert torch.allclose(tp[-1], thK, atol=1e-7)
 
-    np.savez(path, n=n, d_in=d_in, d_out=d_out, K=K, theta0=f32(th0), target=f32(tgt),
-             text_syn=f32(text_syn), lr_img=f32(lr_img), lr_txt=f32(lr_txt),
-             xs=np.stack([f32(x) for x in xs]), perms=np.stack([p.numpy() for p in perms]),
-             ces=np.array(ces, np.float32), grand=f32(grand), theta_K=f32(thK),
-             g_text_syn=f32(g_txt), g_lr_img=f32(g_s), g_lr_txt=f32(g_lr))
+    # theta0 is regenerated by the tests (seed 11, the oracle's ProjectionHead, the two LayerNorm offsets above)
+    rec = dict(n=n, d_in=d_in, d_out=d_out, K=K, seed=11, target=f32(tgt),
+               text_syn=f32(text_syn), lr_img=f32(lr_img), lr_txt=f32(lr_txt),
+               xs=np.stack([f32(x) for x in xs]), perms=np.stack([p.numpy() for p in perms]),
+               ces=np.array(ces, np.float32), grand=f32(grand), theta_K=f32(thK),
+               g_text_syn=f32(g_txt), g_lr_img=f32(g_s), g_lr_txt=f32(g_lr))
+    fingerprint(rec, "theta0", th0)
+    np.savez(path, **rec)
     print("wrote", path, "grand", grand.item())
 
 
@@ -186,9 +201,10 @@ def gen_unroll(ReparamModule, RefHead, path, variant, n, size, d_txt, K, outer_i
                sig_txt=sig_txt)
     rec["image_syn0"] = f32(image_syn) if full else f32(image_syn[:, :, :4, :4])
     rec["text_syn0"] = f32(text_syn)
-    if full:
-        rec["theta0_img"], rec["theta0_txt"] = f32(th0_img), f32(th0_txt)
-        rec["target_img"], rec["target_txt"] = f32(tgt_img), f32(tgt_txt)
+    if full:   # the tests regenerate these from `seed` and `sig_*` (tests/golden_inputs.py)
+        for key, t in (("theta0_img", th0_img), ("theta0_txt", th0_txt), ("target_img", tgt_img),
+                       ("target_txt", tgt_txt)):
+            fingerprint(rec, key, t)
     all_perms = []
     for it in range(outer_its):
         perms = [torch.randperm(n, generator=pg) for _ in range(K)]
@@ -282,11 +298,37 @@ def gen_nearest_neighbor(path):
     print("wrote", path, "hits on the planted rows:", int((idx == pick).sum()), "of", q)
 
 
+def gen_reparam(ReparamModule, path):
+    """Flatten-order golden: the reference's own ReparamModule around the oracle's ProjectionHead(16, 24) and around
+    the two-layer toy of tests/test_reparam_cpu.py -- its parameter table, its forward through a given flat theta
+    and (toy) the derivative of that output w.r.t. theta."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_reparam_cpu import Toy
+    rec = {}
+    for tag, module, d_in, rows, seed in (("head", dr.ProjectionHead(16, 24), 16, 5, 0), ("toy", Toy(), 4, 3, 1)):
+        rm = ReparamModule(module)
+        rec[tag + "_info_module"] = np.array([m for m, _ in rm._param_infos])
+        rec[tag + "_info_name"] = np.array([n for _, n in rm._param_infos])
+        rec[tag + "_numels"] = np.array(rm._param_numels, np.int64)
+        rec[tag + "_shape_ndim"] = np.array([len(s) for s in rm._param_shapes], np.int64)
+        rec[tag + "_shape_dims"] = np.array([d for s in rm._param_shapes for d in s], np.int64)
+        g = torch.Generator().manual_seed(seed)
+        th = torch.randn(sum(rm._param_numels), generator=g).requires_grad_(True)
+        x = torch.randn(rows, d_in, generator=g)
+        y = rm(x, flat_param=th)
+        gth, = torch.autograd.grad(y.sum(), th)
+        rec[tag + "_theta"], rec[tag + "_x"], rec[tag + "_y"], rec[tag + "_g_theta"] = f32(th), f32(x), f32(y), f32(gth)
+    np.savez(path, **rec)
+    print("wrote", path)
+
+
 def main():
     out = os.path.join(ROOT, "tests", "golden")
     os.makedirs(out, exist_ok=True)
     ReparamModule, RefHead = load_reference_pieces()
-    which = sys.argv[1:] or ["text", "tiny", "c1", "itm", "nn"]
+    which = sys.argv[1:] or ["text", "tiny", "c1", "itm", "nn", "reparam"]
+    if "reparam" in which:
+        gen_reparam(ReparamModule, os.path.join(out, "reparam_reference.npz"))
     if "nn" in which:
         gen_nearest_neighbor(os.path.join(out, "nearest_neighbor_small.npz"))
     if "itm" in which:

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, rel_err
+from golden_inputs import text_only_theta0, unroll_params
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +34,8 @@ def test_autograd_dropin_matches_golden_tiny(report):
                              variant="nfnet_tiny", syn_steps=K, dtype="f32")
     img_net, txt_net = ReparamModule(enc).to(dev), ReparamModule(head).to(dev)
     img_net.train(), txt_net.train()
-    assert img_net.param_numel == g["theta0_img"].size and txt_net.param_numel == g["theta0_txt"].size
+    th0i, th0t, tgi, tgt = (t.to(dev) for t in unroll_params(g))
+    assert img_net.param_numel == th0i.numel() and txt_net.param_numel == th0t.numel()
     T = lambda k: torch.from_numpy(g[k]).to(dev)
     image_syn = T("image_syn0").requires_grad_(True)
     text_syn = T("text_syn0").requires_grad_(True)
@@ -41,8 +43,7 @@ def test_autograd_dropin_matches_golden_tiny(report):
     lrt = torch.tensor(0.1, device=dev, requires_grad=True)
     perms = [torch.from_numpy(p).to(dev) for p in g["perms"][0]]
     grand, il, tl, ces = reference_loop_iteration(img_net, txt_net, image_syn, text_syn, lri, lrt,
-                                                  T("theta0_img"), T("theta0_txt"), T("target_img"),
-                                                  T("target_txt"), perms)
+                                                  th0i, th0t, tgi, tgt, perms)
     grand.backward()                                   # reference distill.py:606
     e = dict(grand=abs(grand.item() - g["it0_grand"]) / abs(g["it0_grand"]),
              ces=rel_err(torch.stack(ces), torch.from_numpy(g["it0_ces"])),
@@ -67,9 +68,10 @@ def test_text_only_golden_through_hip_ops(report):
     dev = "cuda"
     eng = UnrollEngine("nfnet_tiny", batch=n, num_queries=n, image_size=32, d_txt=d_in, syn_steps=K,
                        dtype="f32")
-    assert eng.feature_dim == d_out and eng.P_txt == g["theta0"].size
+    th0 = text_only_theta0(g).to(dev)
+    assert eng.feature_dim == d_out and eng.P_txt == th0.numel()
     T = lambda k: torch.from_numpy(g[k]).to(dev)
-    th0, tgt = T("theta0"), T("target")
+    tgt = T("target")
     text = T("text_syn").requires_grad_(True)
     s = torch.tensor(float(g["lr_img"]), device=dev, requires_grad=True)
     lrt = torch.tensor(float(g["lr_txt"]), device=dev, requires_grad=True)

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, rel_err
+from golden_inputs import unroll_params
 
 pytestmark = pytest.mark.gpu
 
@@ -224,7 +225,7 @@ def test_unrolled_match_golden_tiny(dtype, report):
     T = lambda k: torch.from_numpy(g[k]).to(dev)
     image_syn, text_syn = T("image_syn0").clone(), T("text_syn0").clone()
     lr = torch.tensor([0.1, 0.1], device=dev)
-    th0i, th0t, tgi, tgt = T("theta0_img"), T("theta0_txt"), T("target_img"), T("target_txt")
+    th0i, th0t, tgi, tgt = (t.to(dev) for t in unroll_params(g))
     bufs = [torch.zeros_like(image_syn), torch.zeros_like(text_syn), torch.zeros(2, device=dev)]
     lib = _lib.load()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)

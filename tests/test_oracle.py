@@ -1,10 +1,8 @@
 """CPU tests of the oracle (the checker itself): structural anchors of the NFNet restatement, the
 restated loop against the committed golden fixtures (which were produced with the reference's own
-ReparamModule + ProjectionHead, oracle/gen_golden.py), optimiser semantics, and -- when the
-reference checkout is present (build container only) -- the restatement against the reference's
-importable pieces directly."""
+ReparamModule + ProjectionHead, oracle/gen_golden.py), optimiser semantics, and the restatement against what the reference's own ReparamModule computed
+(tests/golden/reparam_reference.npz)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -12,10 +10,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, rel_err
+from golden_inputs import reparam_shapes, text_only_theta0, unroll_params
 from oracle import distill_ref as dr
 from oracle import nfnet_ref as nr
-
-REF = "/root/reference"
 
 
 def test_nfnet_l0_structural_anchors():
@@ -65,7 +62,7 @@ def test_restated_loop_matches_golden_text_only():
     g = np.load(os.path.join(GOLDEN, "text_only_unroll.npz"))
     n, d_in, d_out, K = int(g["n"]), int(g["d_in"]), int(g["d_out"]), int(g["K"])
     ft = dr.FlatModule(dr.ProjectionHead(d_in, d_out))
-    th0, tgt = torch.from_numpy(g["theta0"]), torch.from_numpy(g["target"])
+    th0, tgt = text_only_theta0(g), torch.from_numpy(g["target"])
     text = torch.from_numpy(g["text_syn"]).requires_grad_(True)
     s = torch.tensor(float(g["lr_img"]), requires_grad=True)
     lrt = torch.tensor(float(g["lr_txt"]), requires_grad=True)
@@ -95,12 +92,12 @@ def test_restated_loop_matches_golden_tiny_two_iterations():
     img, txt = T("image_syn0").clone(), T("text_syn0").clone()
     lr = torch.tensor([0.1, 0.1])
     opt = [dr.SGDMomentum(1000.0), dr.SGDMomentum(1000.0), dr.SGDMomentum(1e-3)]
+    th0i, th0t, tgi, tgt = unroll_params(g)
     for it in range(2):
         ir, tr = img.clone().requires_grad_(True), txt.clone().requires_grad_(True)
         li, lt = lr[0].clone().requires_grad_(True), lr[1].clone().requires_grad_(True)
         perms = [torch.from_numpy(p) for p in g["perms"][it]]
-        grand, aux = dr.unrolled_match(fi, ft, ir, tr, li, lt, T("theta0_img"), T("theta0_txt"),
-                                       T("target_img"), T("target_txt"), perms)
+        grand, aux = dr.unrolled_match(fi, ft, ir, tr, li, lt, th0i, th0t, tgi, tgt, perms)
         gi, gt, gli, glt = dr.outer_grads(grand, ir, tr, li, lt)
         assert abs(grand.item() - float(g[f"it{it}_grand"])) < 1e-5 * abs(float(g[f"it{it}_grand"]))
         assert rel_err(gi, T(f"it{it}_g_image_syn")) < 1e-4
@@ -111,21 +108,18 @@ def test_restated_loop_matches_golden_tiny_two_iterations():
         assert rel_err(lr, T(f"it{it}_lr_after")) < 1e-5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout only exists in the build container")
 def test_flat_module_matches_reference_reparam_module():
-    sys.path.insert(0, REF)
-    import reparam_module  # the reference's own file (torch-only)
+    """tests/golden/reparam_reference.npz holds the reference's own ReparamModule around the same
+    ProjectionHead(16, 24): its parameter table and its output through a given flat theta
+    (oracle/gen_golden.py gen_reparam)."""
+    g = np.load(os.path.join(GOLDEN, "reparam_reference.npz"))
     torch.manual_seed(0)
-    a = dr.ProjectionHead(16, 24)
-    b = dr.ProjectionHead(16, 24)
-    b.load_state_dict(a.state_dict())
-    fm = dr.FlatModule(a)
-    rm = reparam_module.ReparamModule(b)
-    assert tuple(fm.numels) == rm._param_numels
-    assert [tuple(s) for s in rm._param_shapes] == fm.shapes
-    th = torch.randn(fm.param_numel)
-    x = torch.randn(5, 16)
-    assert torch.allclose(fm(x, flat_param=th), rm(x, flat_param=th), atol=1e-6)
+    fm = dr.FlatModule(dr.ProjectionHead(16, 24))
+    assert tuple(fm.numels) == tuple(g["head_numels"].tolist())
+    assert reparam_shapes(g, "head") == fm.shapes
+    th, x = torch.from_numpy(g["head_theta"]), torch.from_numpy(g["head_x"])
+    assert th.numel() == fm.param_numel
+    assert torch.allclose(fm(x, flat_param=th), torch.from_numpy(g["head_y"]), atol=1e-6)
 
 
 def test_retrieval_oracle_matches_reference_itm_eval_golden():
@@ -246,12 +240,12 @@ def test_squeeze_excite_gate_from_the_mid_channel_pooled_vector():
 def test_goldens_are_present_and_well_formed():
     """Every fixture the GPU suite compares against exists, loads without pickle, and holds finite numbers
     (tests/golden/*.npz are written by oracle/gen_golden.py in the build container: the GPU box never sees the reference)."""
-    want = {"unroll_tiny": ["it0_grand", "it1_grand", "theta0_img", "perms"],
+    want = {"unroll_tiny": ["it0_grand", "it1_grand", "theta0_img_sample", "perms"],
             "unroll_c1_scalars": ["it0_grand", "it0_g_image_syn_slice", "it0_g_text_syn"],
             "unroll_c2s_scalars": ["it0_grand", "it0_g_image_syn_slice", "it0_text_syn_after"],
             "unroll_k8_scalars": ["it0_grand", "it0_ces", "it0_g_image_syn_slice", "it0_text_syn_after", "perms"],
-            "text_only_unroll": ["grand", "g_text_syn"], "itm_eval_small": ["rank_i2t"],
-            "nearest_neighbor_small": ["index"]}
+            "text_only_unroll": ["grand", "g_text_syn", "theta0_sample"], "itm_eval_small": ["rank_i2t"],
+            "nearest_neighbor_small": ["index"], "reparam_reference": ["head_y", "toy_y", "toy_g_theta"]}
     for name, keys in want.items():
         g = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
         for k in keys:

@@ -1,13 +1,14 @@
 """Host-logic tests of the product ReparamModule (generic split/view path runs on CPU; the native
 HIP path is covered by the -m gpu tests)."""
 import os
-import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
-REF = "/root/reference"
+from conftest import GOLDEN
+from golden_inputs import reparam_infos, reparam_shapes
 
 
 class Toy(nn.Module):
@@ -44,25 +45,23 @@ def test_flatten_order_views_and_double_backward():
     assert torch.allclose(rm(x), rm(x, flat_param=rm.flat_param))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout only exists in the build container")
 def test_matches_reference_reparam_module():
+    """Against tests/golden/reparam_reference.npz: the reference's own ReparamModule around this Toy -- its
+    parameter table, its output through a given flat theta and that output's derivative w.r.t. theta."""
     from multimodal_dataset_distillation_amd.reparam_module import ReparamModule
-    sys.path.insert(0, REF)
-    import reparam_module as ref
+    g = np.load(os.path.join(GOLDEN, "reparam_reference.npz"))
     torch.manual_seed(1)
-    a, b = Toy(), Toy()
-    b.load_state_dict(a.state_dict())
-    mine, theirs = ReparamModule(a), ref.ReparamModule(b)
-    assert mine._param_infos == theirs._param_infos
-    assert mine._param_numels == theirs._param_numels
-    assert tuple(mine._param_shapes) == tuple(theirs._param_shapes)
-    th = torch.randn(mine.param_numel, requires_grad=True)
-    x = torch.randn(3, 4)
-    y1, y2 = mine(x, flat_param=th), theirs(x, flat_param=th)
-    assert torch.allclose(y1, y2, atol=1e-7)
+    mine = ReparamModule(Toy())
+    assert mine._param_infos == reparam_infos(g, "toy")
+    assert mine._param_numels == tuple(g["toy_numels"].tolist())
+    assert tuple(tuple(s) for s in mine._param_shapes) == tuple(reparam_shapes(g, "toy"))
+    th = torch.from_numpy(g["toy_theta"]).requires_grad_(True)
+    x = torch.from_numpy(g["toy_x"])
+    assert th.numel() == mine.param_numel
+    y1 = mine(x, flat_param=th)
+    assert torch.allclose(y1, torch.from_numpy(g["toy_y"]), atol=1e-7)
     g1, = torch.autograd.grad(y1.sum(), th, create_graph=True)
-    g2, = torch.autograd.grad(y2.sum(), th, create_graph=True)
-    assert torch.allclose(g1, g2, atol=1e-7)
+    assert torch.allclose(g1, torch.from_numpy(g["toy_g_theta"]), atol=1e-7)
 
 
 def test_expert_buffer_roundtrip(tmp_path):
