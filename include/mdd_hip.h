@@ -48,7 +48,8 @@ extern "C" {
 typedef struct mdd_engine mdd_engine;
 
 typedef struct mdd_config {
-  const char* variant; /* "nfnet_l0" | "nfnet_l1" | "nfnet_tiny" */
+  const char* variant; /* "nfnet_l0" | "nfnet_l1" | "nfnet_tiny" | "nf_resnet50" | "nf_resnet_tiny" | "vit_b16" |
+                          "vit_tiny16" | "vit_tiny16_cls" | "vit_micro" | "vit_micro_cls"                  */
   int32_t batch;       /* pairs per inner step (mini_batch_size, distill.py:511)          */
   int32_t num_queries; /* rows of image_syn / text_syn (distill.py:630)                    */
   int32_t image_size;  /* square input, multiple of 32                                     */
@@ -65,9 +66,9 @@ typedef struct mdd_config {
 
 const char* mdd_last_error(void);
 /* ABI version of this header: 2 = round 2 (mdd_config.keep_steps, MDD_DTYPE_BF16X2 / _F32_BF16OPS,
- * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels.  A binding built against another version
+ * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2.  A binding built against another version
  * must refuse to load. */
-#define MDD_ABI_VERSION 6
+#define MDD_ABI_VERSION 7
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
  * pipelined kernels; 0 routes them to the general kernels instead (process-wide; returns the previous setting).  For the
@@ -209,6 +210,16 @@ int mdd_op_conv2d_wgrad2(int dtype, int nimg, int hin, int win, int cin, int cou
                          int pad, int groups, const void* dy1_dev, const void* x1_dev, const void* dy2_dev,
                          const void* x2_dev, float* dw_packed_dev, float* dbias_dev, float* ws_dev,
                          long long ws_floats, void* stream);
+/* MaxPool2d(3, stride 2, padding 1) on NHWC [n, h, w, c] (the NF-ResNet stem's pool); ho = (h - 1) / 2 + 1, the same
+ * for w.  c must be a multiple of 4 (MDD_DTYPE_F32) or 8 (MDD_DTYPE_BF16).  idx: [n, ho, wo, c] bytes, ky*3 + kx of
+ * the FIRST maximum of each window (PyTorch's rule: taps in row-major order, a tap wins when greater or NaN;
+ * padding is -inf).
+ *   mode 0  forward:  x [n, h, w, c] -> y [n, ho, wo, c], writes idx
+ *   mode 1  tangent:  x = x_t [n, h, w, c] -> y = y_t [n, ho, wo, c], the element at idx
+ *   mode 2  backward (and tangent backward, the index being fixed): x = dy [n, ho, wo, c] -> y = dx [n, h, w, c],
+ *           each input element gathers the windows whose index points at it (no atomics) */
+int mdd_op_maxpool2d_3s2(int dtype, int mode, int n, int h, int w, int c, const void* x_dev, void* y_dev,
+                         void* idx_dev, void* stream);
 
 /* ---- synthetic-set evaluation: retrieval ranks.
  * Replaces the per-row host loops of reference epoch.py:140-156 (image->text: argsort of one similarity

@@ -14,7 +14,10 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmdd_hip.so")
 SOURCES = ["flat_ops.hip", "ws.hip", "elementwise.hip", "linear.hip", "head.hip", "conv_gemm.hip",
-           "conv_wgrad.hip", "retrieval.hip", "collective.hip", "vit.hip", "attn.hip", "engine.hip"]
+           "conv_gemm_relu.hip", "conv_wgrad.hip", "retrieval.hip", "collective.hip", "vit.hip", "attn.hip",
+           "nfres.hip", "engine.hip"]
+# sources that include another source file: rebuilt when it changes
+INCLUDES = {"conv_gemm_relu.hip": ["conv_gemm.hip"]}
 HEADERS = ["common.h", "kernels.h", "engine.h", "conv_gemm_epilogue.inc", os.path.join("..", "..", "include", "mdd_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result",
          "-I", os.path.join(HERE, "..", "include")]
@@ -68,7 +71,7 @@ def build(verbose=True, force=False):
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s + ".o")
         stamp = obj + ".sha1"
-        dig = _digest([src]) + hdig
+        dig = _digest([src] + [os.path.join(CSRC, d) for d in INCLUDES.get(s, [])]) + hdig
         objs.append(obj)
         if (not force and os.path.exists(obj) and os.path.exists(stamp)
                 and open(stamp).read() == dig):

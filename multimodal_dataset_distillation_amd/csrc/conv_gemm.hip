@@ -17,6 +17,9 @@
 // of a ds_read_b128 hits 16 distinct 16-byte slots of the 256-byte bank row (conflict-free).
 // bf16: v_mfma_f32_32x32x16_bf16 ; f32 (parity mode): v_mfma_f32_32x32x2_f32 (exact fp32 FMA).
 // Fused epilogues (ConvEpi): bias, SiLU*beta, SiLU' / SiLU'' chain rule, residual adds.
+// ReLU epilogues (NF-ResNet, ConvEpi::act == 3) are instances of the same kernels compiled in a translation unit of
+// their own (conv_gemm_relu.hip includes this file with MDD_CONV_GEMM_RELU_TU defined): launch_conv_gemm hands such a
+// launch to launch_conv_gemm_relu.
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
@@ -188,15 +191,19 @@ DEVI void epi_wave_sync() {
 }
 
 // activation of the fused epilogues: 0 = SiLU (NFNet), 1 = exact GELU (the ViT MLP: fc1's forward and fc2's data gradient)
-// (2 = the same GELU through the 1.5e-7 erf approximation: bf16 storage only, k_gemm_pipe)
+// (2 = the same GELU through the 1.5e-7 erf approximation: bf16 storage only, k_gemm_pipe), 3 = ReLU (NF-ResNet: its
+// derivative is the step 1[x > 0], its second derivative 0)
 template <int ACT> DEVI float actf(float x) {
-  if constexpr (ACT == 2) return gelu_fast_(x); else if constexpr (ACT == 1) return gelu_(x); else return silu_(x);
+  if constexpr (ACT == 3) return relu_(x);
+  else if constexpr (ACT == 2) return gelu_fast_(x); else if constexpr (ACT == 1) return gelu_(x); else return silu_(x);
 }
 template <int ACT> DEVI float dactf(float x) {
-  if constexpr (ACT == 2) return dgelu_fast_(x); else if constexpr (ACT == 1) return dgelu_(x); else return dsilu_(x);
+  if constexpr (ACT == 3) return x > 0.f ? 1.f : 0.f;
+  else if constexpr (ACT == 2) return dgelu_fast_(x); else if constexpr (ACT == 1) return dgelu_(x); else return dsilu_(x);
 }
 template <int ACT> DEVI Dual dactf(Dual x) {
-  if constexpr (ACT == 2) return dgelu_fast_(x); else if constexpr (ACT == 1) return dgelu_(x); else return dsilu_(x);
+  if constexpr (ACT == 3) return Dual(x.v > 0.f ? 1.f : 0.f, 0.f);
+  else if constexpr (ACT == 2) return dgelu_fast_(x); else if constexpr (ACT == 1) return dgelu_(x); else return dsilu_(x);
 }
 
 template <class AT, int WGM, int WGN, int TM, int TN, int MODE, bool KFULL, int PREC, bool IBK = false, int ACT = 0>
@@ -620,6 +627,7 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
                              // stashed tensors per output tile) run on k_gemm_pipe too.  Per-launch it looks slower -- with one block
                              // per CU nothing overlaps those HBM-bound epilogues (312 vs 232 us per launch inside configs[4]) -- but the iteration is faster with it (426 vs 445 ms): 0 is kept for the record
 #endif
+#ifndef MDD_CONV_GEMM_RELU_TU   // (the ReLU translation unit has no pipelined-kernel launches: see launch_conv_gemm_)
 template <int N_> DEVI void wait_vm() {
   __builtin_amdgcn_s_waitcnt((N_ & 0xF) | ((N_ >> 4) << 14) | (0x7 << 4) | (0xF << 8));
 }
@@ -795,6 +803,7 @@ bool launch_pipe_gemm(const KArgs& a, hipStream_t st) {
   else k_gemm_pipe<0><<<blocks, 512, 131072, st>>>(k);
   return true;
 }
+#endif  // MDD_CONV_GEMM_RELU_TU
 
 template <class AT, int WGM, int WGN, int TM, int TN, int MODE, bool KFULL, int PREC, bool IBK = false, int ACT = 0>
 void launch_cfg(const KArgs& a, hipStream_t st) {
@@ -822,11 +831,12 @@ void launch_cfg(const KArgs& a, hipStream_t st) {
   k_conv_gemm<AT, WGM, WGN, TM, TN, MODE, KFULL, PREC, IBK, ACT><<<(unsigned)blocks, 256, shm, st>>>(k);
 }
 
-}  // namespace
-
-template <class AT>
-void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
-                      const ConvEpi& ep, hipStream_t st) {
+// ACTV = 0: every launch but the ReLU epilogues (SiLU / GELU / no activation); ACTV = 3: the ReLU epilogues (their own
+// instances of the same kernels -- a run-time switch inside the SiLU instances cost NFNet +10 %, round 2 -- with the same
+// tile choice; no pipelined kernel and no per-image bias, which only squeeze-excite blocks use)
+template <class AT, int ACTV>
+void launch_conv_gemm_(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
+                       const ConvEpi& ep, hipStream_t st) {
   KArgs a;
   a.A1 = A1; a.B1 = B1; a.A2 = A2; a.B2 = B2;
   a.g = g; a.ep = ep;
@@ -846,23 +856,24 @@ void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A
   const int mode = pw ? 0 : (s2t ? (((g.ho | g.wo) & 1) == 0 && g.k <= 3 ? 2 : 3) : 1);
   const bool kfull = ((g.k * g.k * g.kc) % Mma<AT>::KE) == 0;
   // per-image bias (ConvEpi::ib): pointwise data gradients with an activation epilogue only
-  const bool ibk = ep.ib != nullptr && mode == 0 && (ep.mode == EPI_BWD || ep.mode == EPI_BWD_T);
+  const bool ibk = ACTV == 0 && ep.ib != nullptr && mode == 0 && (ep.mode == EPI_BWD || ep.mode == EPI_BWD_T);
   if constexpr (sizeof(AT) == 2) {
     // MODE 4: 3x3 stride-1 "same" conv (forward or data gradient) whose group is one 128-byte channel row
     const bool slab = g.k == 3 && g.stride == 1 && g.pad == 1 && g.kc == 64 && g.nc <= 64 && g.ha == g.ho &&
                       g.wa == g.wo && (size_t)(256 + 2 * g.wo + 3) * 128 + 3 * 64 * 128 <= MODE4_MAX_LDS;
-    if (slab) { launch_cfg<AT, 4, 1, 2, 2, 4, true, 0>(a, st); return; }
+    if (slab) { launch_cfg<AT, 4, 1, 2, 2, 4, true, 0, false, ACTV>(a, st); return; }
   }
 #define MDD_DISPATCH_P(WGM, WGN, TM, TN, PREC)                                                \
   do {                                                                                        \
-    if (mode == 0 && ibk) { if (kfull) launch_cfg<AT, WGM, WGN, TM, TN, 0, true, PREC, true>(a, st);   \
-                            else launch_cfg<AT, WGM, WGN, TM, TN, 0, false, PREC, true>(a, st); }      \
-    else if (mode == 0) { if (kfull) launch_cfg<AT, WGM, WGN, TM, TN, 0, true, PREC>(a, st);            \
-                     else launch_cfg<AT, WGM, WGN, TM, TN, 0, false, PREC>(a, st); }         \
-    else if (mode == 1) { if (kfull) launch_cfg<AT, WGM, WGN, TM, TN, 1, true, PREC>(a, st); \
-                          else launch_cfg<AT, WGM, WGN, TM, TN, 1, false, PREC>(a, st); }    \
-    else if (mode == 2) launch_cfg<AT, WGM, WGN, TM, TN, 2, false, PREC>(a, st);             \
-    else launch_cfg<AT, WGM, WGN, TM, TN, 3, false, PREC>(a, st);                            \
+    if (mode == 0 && ibk) { if constexpr (ACTV == 0) {                                        \
+                            if (kfull) launch_cfg<AT, WGM, WGN, TM, TN, 0, true, PREC, true>(a, st);   \
+                            else launch_cfg<AT, WGM, WGN, TM, TN, 0, false, PREC, true>(a, st); } }    \
+    else if (mode == 0) { if (kfull) launch_cfg<AT, WGM, WGN, TM, TN, 0, true, PREC, false, ACTV>(a, st);            \
+                     else launch_cfg<AT, WGM, WGN, TM, TN, 0, false, PREC, false, ACTV>(a, st); }         \
+    else if (mode == 1) { if (kfull) launch_cfg<AT, WGM, WGN, TM, TN, 1, true, PREC, false, ACTV>(a, st); \
+                          else launch_cfg<AT, WGM, WGN, TM, TN, 1, false, PREC, false, ACTV>(a, st); }    \
+    else if (mode == 2) launch_cfg<AT, WGM, WGN, TM, TN, 2, false, PREC, false, ACTV>(a, st);             \
+    else launch_cfg<AT, WGM, WGN, TM, TN, 3, false, PREC, false, ACTV>(a, st);                            \
   } while (0)
 #define MDD_DISPATCH(WGM, WGN, TM, TN)                                                        \
   do {                                                                                        \
@@ -873,6 +884,7 @@ void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A
     }                                                                                         \
     MDD_DISPATCH_P(WGM, WGN, TM, TN, 0);                                                      \
   } while (0)
+#ifndef MDD_CONV_GEMM_RELU_TU
   if constexpr (sizeof(AT) == 2) {
     if (launch_pipe_gemm(a, st)) return;
   }
@@ -888,6 +900,7 @@ void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A
     else launch_cfg<AT, 2, 2, 2, 2, 0, false, 0, false, 1>(a, st);
     return;
   }
+#endif
   if (g.nc <= 32) MDD_DISPATCH(4, 1, 1, 1);        // 128 x 32  (stem)
   else if (g.nc <= 64) MDD_DISPATCH(4, 1, 2, 2);   // 256 x 64  (group width 64)
 #if MDD_BIG_TILE == 0
@@ -900,6 +913,16 @@ void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A
 #undef MDD_DISPATCH
 #undef MDD_DISPATCH_P
 }
+
+}  // namespace
+
+#ifndef MDD_CONV_GEMM_RELU_TU
+template <class AT>
+void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
+                      const ConvEpi& ep, hipStream_t st) {
+  if (ep.act == 3 && (ep.out_act || ep.mode == EPI_BWD_T)) { launch_conv_gemm_relu<AT>(g, A1, B1, A2, B2, ep, st); return; }
+  launch_conv_gemm_<AT, 0>(g, A1, B1, A2, B2, ep, st);
+}
 // GELU epilogues: pointwise contractions on the 128 x 128 tile (output width per group > 64)
 static std::atomic<int> g_pipe_on{1};
 bool pipe_kernels_enabled() { return g_pipe_on.load(std::memory_order_relaxed) != 0; }
@@ -911,3 +934,14 @@ template void launch_conv_gemm<float>(const ConvGeom&, const float*, const float
                                       const float*, const ConvEpi&, hipStream_t);
 template void launch_conv_gemm<bf16>(const ConvGeom&, const bf16*, const bf16*, const bf16*,
                                      const bf16*, const ConvEpi&, hipStream_t);
+#else
+template <class AT>
+void launch_conv_gemm_relu(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
+                           const ConvEpi& ep, hipStream_t st) {
+  launch_conv_gemm_<AT, 3>(g, A1, B1, A2, B2, ep, st);
+}
+template void launch_conv_gemm_relu<float>(const ConvGeom&, const float*, const float*, const float*,
+                                           const float*, const ConvEpi&, hipStream_t);
+template void launch_conv_gemm_relu<bf16>(const ConvGeom&, const bf16*, const bf16*, const bf16*,
+                                          const bf16*, const ConvEpi&, hipStream_t);
+#endif

@@ -256,7 +256,7 @@ __global__ void k_avgpool2_bwd(AT* __restrict__ din, const AT* __restrict__ dout
 }
 
 // ------------------------------------------------------------------ per-(n,c) reductions over h*w
-// block = 256 threads = 8 chunk columns x 32 hw lanes.  MODE 0: mean x ; 1: mean silu(x) ;
+// block = 256 threads = 8 chunk columns x 32 hw lanes.  MODE 0: mean x ; 1: mean silu(x) ; 4: mean relu(x) ;
 // 2: d = ga * sum a*b, then the sigmoid backward of the SE gate: out = d*g*(1-g)
 // 3: MODE 2, and the gradient w.r.t. conv3's output is written in the same pass: cb = a * g * ga
 //    (a = grad of the block output, b = conv3 output; the pooled path's share of that gradient reaches the
@@ -298,6 +298,9 @@ __global__ void k_hw_reduce(float* __restrict__ out, float* __restrict__ out_t,
       } else if constexpr (MODE == 1) {
 #pragma unroll
         for (int e = 0; e < CE; ++e) acc[e] = acc[e] + silu_(x[e]);
+      } else if constexpr (MODE == 4) {
+#pragma unroll
+        for (int e = 0; e < CE; ++e) acc[e] = acc[e] + relu_(x[e]);
       } else {
 #pragma unroll
         for (int e = 0; e < CE; ++e) acc[e] = acc[e] + x[e] * y[e];
@@ -306,18 +309,18 @@ __global__ void k_hw_reduce(float* __restrict__ out, float* __restrict__ out_t,
     int p = lane;
     for (; p + 32 < hw; p += 64) {
       const int64_t c0 = ((int64_t)ni * hw + p) * cch + col, c1 = c0 + (int64_t)32 * cch;
-      S x0[CE], x1[CE], y0[MODE >= 2 ? CE : 1], y1[MODE >= 2 ? CE : 1];
+      S x0[CE], x1[CE], y0[MODE == 2 || MODE == 3 ? CE : 1], y1[MODE == 2 || MODE == 3 ? CE : 1];
       ld_chunkS<S, AT>(a, a_t, c0, x0);
       ld_chunkS<S, AT>(a, a_t, c1, x1);
-      if constexpr (MODE >= 2) { ld_chunkS<S, AT>(b, b_t, c0, y0); ld_chunkS<S, AT>(b, b_t, c1, y1); }
+      if constexpr (MODE == 2 || MODE == 3) { ld_chunkS<S, AT>(b, b_t, c0, y0); ld_chunkS<S, AT>(b, b_t, c1, y1); }
       body(x0, y0, c0);
       body(x1, y1, c1);
     }
     if (p < hw) {
       const int64_t c0 = ((int64_t)ni * hw + p) * cch + col;
-      S x0[CE], y0[MODE >= 2 ? CE : 1];
+      S x0[CE], y0[MODE == 2 || MODE == 3 ? CE : 1];
       ld_chunkS<S, AT>(a, a_t, c0, x0);
-      if constexpr (MODE >= 2) ld_chunkS<S, AT>(b, b_t, c0, y0);
+      if constexpr (MODE == 2 || MODE == 3) ld_chunkS<S, AT>(b, b_t, c0, y0);
       body(x0, y0, c0);
     }
   }
@@ -342,7 +345,7 @@ __global__ void k_hw_reduce(float* __restrict__ out, float* __restrict__ out_t,
     }
     int64_t oi = (int64_t)ni * c + (int64_t)ccol * CE + e;
     S r = mk<S>(sv * mul, stn * mul);
-    if constexpr (MODE >= 2) {
+    if constexpr (MODE == 2 || MODE == 3) {
       S g = ldS<S>(gate, gate_t, oi);
       r = r * g * (1.f - g);
     }
@@ -406,8 +409,8 @@ __global__ void k_se_apply_bwd(AT* __restrict__ c3bar, AT* __restrict__ c3bar_t,
     st_chunkS<S, AT>(c3bar, c3bar_t, i, o);
   }
 }
-// cfbar = ybar/hw * dsilu(cf)
-template <class S, class AT>
+// cfbar = ybar/hw * dsilu(cf)   (RELU: ybar/hw * 1[cf > 0], whose derivative is 0)
+template <class S, class AT, bool RELU = false>
 __global__ void k_final_pool_bwd(AT* __restrict__ cfbar, AT* __restrict__ cfbar_t,
                                  const float* __restrict__ ybar, const float* __restrict__ ybar_t,
                                  const AT* __restrict__ cf, const AT* __restrict__ cf_t,
@@ -425,7 +428,8 @@ __global__ void k_final_pool_bwd(AT* __restrict__ cfbar, AT* __restrict__ cfbar_
     for (int e = 0; e < CE; ++e) {
       size_t gi = (size_t)ni * c + cc * CE + e;
       S yb = ldS<S>(ybar, ybar_t, gi);
-      o[e] = yb * rhw * dsilu_(x[e]);
+      if constexpr (RELU) o[e] = val(x[e]) > 0.f ? yb * rhw : mk<S>(0.f, 0.f);
+      else o[e] = yb * rhw * dsilu_(x[e]);
     }
     st_chunkS<S, AT>(cfbar, cfbar_t, i, o);
   }
@@ -505,7 +509,7 @@ __global__ __launch_bounds__(256) void k_se_apply_bwd_tiled(
     st_chunkS<S, AT>(c3bar, c3bar_t, i, o);
   }
 }
-template <class S, class AT>
+template <class S, class AT, bool RELU = false>
 __global__ __launch_bounds__(256) void k_final_pool_bwd_tiled(
     AT* __restrict__ cfbar, AT* __restrict__ cfbar_t, const float* __restrict__ ybar,
     const float* __restrict__ ybar_t, const AT* __restrict__ cf, const AT* __restrict__ cf_t, int hw,
@@ -522,7 +526,10 @@ __global__ __launch_bounds__(256) void k_final_pool_bwd_tiled(
     S x[CE], o[CE];
     ld_chunkS<S, AT>(cf, cf_t, i, x);
 #pragma unroll
-    for (int e = 0; e < CE; ++e) o[e] = yb[e] * dsilu_(x[e]);
+    for (int e = 0; e < CE; ++e) {
+      if constexpr (RELU) o[e] = val(x[e]) > 0.f ? yb[e] : mk<S>(0.f, 0.f);
+      else o[e] = yb[e] * dsilu_(x[e]);
+    }
     st_chunkS<S, AT>(cfbar, cfbar_t, i, o);
   }
 }
@@ -653,8 +660,17 @@ void launch_se_apply_bwd(AT* c3bar, AT* c3bar_t, const AT* xbar, const AT* xbar_
 }
 template <class AT>
 void launch_final_pool(float* y, float* y_t, const AT* cf, const AT* cf_t, int n, int hw, int c,
-                       hipStream_t st) {
+                       hipStream_t st, bool relu) {
   int colgroups = (c / Chunk<AT>::N + 7) / 8;
+  if (relu) {
+    if (cf_t)
+      k_hw_reduce<Dual, AT, 4><<<n * colgroups, 256, 0, st>>>(y, y_t, cf, cf_t, nullptr, nullptr, nullptr, nullptr,
+                                                              1.f / hw, hw, c);
+    else
+      k_hw_reduce<float, AT, 4><<<n * colgroups, 256, 0, st>>>(y, nullptr, cf, nullptr, nullptr, nullptr, nullptr,
+                                                               nullptr, 1.f / hw, hw, c);
+    return;
+  }
   if (cf_t)
     k_hw_reduce<Dual, AT, 1><<<n * colgroups, 256, 0, st>>>(y, y_t, cf, cf_t, nullptr, nullptr,
                                                             nullptr, nullptr, 1.f / hw, hw, c);
@@ -662,25 +678,31 @@ void launch_final_pool(float* y, float* y_t, const AT* cf, const AT* cf_t, int n
     k_hw_reduce<float, AT, 1><<<n * colgroups, 256, 0, st>>>(y, nullptr, cf, nullptr, nullptr,
                                                              nullptr, nullptr, nullptr, 1.f / hw, hw, c);
 }
-template <class AT>
-void launch_final_pool_bwd(AT* cfbar, AT* cfbar_t, const float* ybar, const float* ybar_t,
-                           const AT* cf, const AT* cf_t, int n, int hw, int c, hipStream_t st) {
+template <class AT, bool RELU>
+void final_pool_bwd_(AT* cfbar, AT* cfbar_t, const float* ybar, const float* ybar_t,
+                     const AT* cf, const AT* cf_t, int n, int hw, int c, hipStream_t st) {
   int64_t total = (int64_t)n * hw * (c / Chunk<AT>::N);
   if (MDD_EW_TILED && tiled_ok(c, Chunk<AT>::N)) {
     int rpb;
     const dim3 grid = tiled_grid(n, hw, c, Chunk<AT>::N, &rpb);
     if (cf_t)
-      k_final_pool_bwd_tiled<Dual, AT><<<grid, 256, 0, st>>>(cfbar, cfbar_t, ybar, ybar_t, cf, cf_t, hw, c, rpb);
+      k_final_pool_bwd_tiled<Dual, AT, RELU><<<grid, 256, 0, st>>>(cfbar, cfbar_t, ybar, ybar_t, cf, cf_t, hw, c, rpb);
     else
-      k_final_pool_bwd_tiled<float, AT><<<grid, 256, 0, st>>>(cfbar, nullptr, ybar, nullptr, cf, nullptr, hw, c, rpb);
+      k_final_pool_bwd_tiled<float, AT, RELU><<<grid, 256, 0, st>>>(cfbar, nullptr, ybar, nullptr, cf, nullptr, hw, c, rpb);
     return;
   }
   if (cf_t)
-    k_final_pool_bwd<Dual, AT><<<egrid(total), 256, 0, st>>>(cfbar, cfbar_t, ybar, ybar_t, cf,
-                                                             cf_t, total, hw, c);
+    k_final_pool_bwd<Dual, AT, RELU><<<egrid(total), 256, 0, st>>>(cfbar, cfbar_t, ybar, ybar_t, cf,
+                                                                   cf_t, total, hw, c);
   else
-    k_final_pool_bwd<float, AT><<<egrid(total), 256, 0, st>>>(cfbar, nullptr, ybar, nullptr, cf,
-                                                              nullptr, total, hw, c);
+    k_final_pool_bwd<float, AT, RELU><<<egrid(total), 256, 0, st>>>(cfbar, nullptr, ybar, nullptr, cf,
+                                                                    nullptr, total, hw, c);
+}
+template <class AT>
+void launch_final_pool_bwd(AT* cfbar, AT* cfbar_t, const float* ybar, const float* ybar_t,
+                           const AT* cf, const AT* cf_t, int n, int hw, int c, hipStream_t st, bool relu) {
+  if (relu) final_pool_bwd_<AT, true>(cfbar, cfbar_t, ybar, ybar_t, cf, cf_t, n, hw, c, st);
+  else final_pool_bwd_<AT, false>(cfbar, cfbar_t, ybar, ybar_t, cf, cf_t, n, hw, c, st);
 }
 #define INST(AT)                                                                                   \
   template void launch_img_gather_nhwc<AT>(AT*, const float*, const int64_t*, int, int, int, int,  \
@@ -705,8 +727,8 @@ void launch_final_pool_bwd(AT* cfbar, AT* cfbar_t, const float* ybar, const floa
                                         const float*, const float*, const float*, float, int, int, \
                                         int, hipStream_t);                                         \
   template void launch_final_pool<AT>(float*, float*, const AT*, const AT*, int, int, int,         \
-                                      hipStream_t);                                                \
+                                      hipStream_t, bool);                                          \
   template void launch_final_pool_bwd<AT>(AT*, AT*, const float*, const float*, const AT*,         \
-                                          const AT*, int, int, int, hipStream_t);
+                                          const AT*, int, int, int, hipStream_t, bool);
 INST(float)
 INST(bf16)

@@ -81,6 +81,12 @@ struct NfCfg {
   int stem_chs, group_size;
   float bottle_ratio, feat_mult, se_rd_ratio;
   float alpha, attn_gain, eps, gamma;
+  // topology switches of the NormFreeNet family (NFNet: the defaults; NF-ResNet: 7x7 stem + max pool, ReLU, no
+  // squeeze-excite, no conv2b, no final conv, classifier kept)
+  int stem_pool = 0;       // stem: 0 'deep_quad' (four 3x3 convs), 1 '7x7_pool' (7x7 / 2 conv, 3x3 / 2 max pool)
+  int relu = 0;            // activation: 0 SiLU, 1 ReLU (gamma above is the activation's)
+  int se = 1, conv2b = 1, final_conv = 1;
+  int classes = 0;         // > 0: classifier Linear(features, classes) after the global pool (features = its logits)
 };
 int make_divisible(double v, int divisor, double round_limit = 0.9) {
   int nv = std::max(divisor, (int)(v + divisor / 2.0) / divisor * divisor);
@@ -101,6 +107,20 @@ bool get_cfg(const char* variant, NfCfg& c) {
     c = base; int d[4] = {1, 2, 2, 1}; int ch[4] = {64, 128, 192, 192};
     memcpy(c.depths, d, sizeof d); memcpy(c.channels, ch, sizeof ch);
     c.stem_chs = 64; c.group_size = 16; return true;
+  }
+  // timm 0.6.7 nfnet.py: nf_resnet50 = _nfres_cfg(depths=(3, 4, 6, 3)): channels (256, 512, 1024, 2048), stem
+  // '7x7_pool' with 64 channels, bottle_ratio 0.25, group_size None, act_layer 'relu' (gamma = _nonlin_gamma['relu']),
+  // no attention layer, no final conv; the reference builds it with pretrained=True and no num_classes=0
+  // (networks.py:669-670), so timm's 1000-way head stays on the model and the features are its logits
+  NfCfg res = {{3, 4, 6, 3}, {256, 512, 1024, 2048}, 64, 0, 0.25f, 1.0f, 0.f,
+               0.2f, 1.0f, 1e-5f, 1.7139588594436646f};
+  res.stem_pool = 1; res.relu = 1; res.se = 0; res.conv2b = 0; res.final_conv = 0; res.classes = 1000;
+  if (!strcmp(variant, "nf_resnet50")) { c = res; return true; }
+  if (!strcmp(variant, "nf_resnet_tiny")) {  // build-defined miniature (tests): stage 0's mid width 64 (bf16 slab conv2),
+    // two blocks in stage 0 (the second one has the identity shortcut)
+    c = res; int d[4] = {2, 1, 1, 1}; int ch[4] = {256, 128, 192, 256};
+    memcpy(c.depths, d, sizeof d); memcpy(c.channels, ch, sizeof ch);
+    c.stem_chs = 16; c.classes = 24; return true;
   }
   return false;
 }
@@ -218,6 +238,9 @@ struct Eng : mdd_engine {
   std::vector<ConvL> convs;
   std::vector<Blk> blks;
   int stem[4], fin;
+  int fpool = 0;           // width of the globally pooled features (= feat unless a classifier follows: NF-ResNet)
+  int ract = 0;            // ConvEpi::act of the residual branches' fused epilogues (0 SiLU, 3 ReLU)
+  ConvL stem_col;          // NF-ResNet: the 7x7 stem as a pointwise contraction over its columns (same packed weights)
   std::vector<int> xh, xc;  // stream spatial dim / channels: X[b], b = 0..nb
   int64_t packed_total = 0;
   int total_rows = 0, total_tiles = 0;
@@ -242,7 +265,10 @@ struct Eng : mdd_engine {
   struct ActSet {
     AT *VCOL = nullptr, *VPE = nullptr, *VCOLB = nullptr, *VPEB = nullptr;   // patch columns, patch embedding (+ grads)
     AT *CLS = nullptr, *CLSN = nullptr, *CLSNB = nullptr, *CLSB = nullptr, *TMP = nullptr;
-    float *hin = nullptr, *hinB = nullptr;     // fp32 copies of the normalised class token / its gradient (classifier head)
+    float *hin = nullptr, *hinB = nullptr;     // classifier input / its gradient (fp32): the ViT's normalised class token,
+                                               // NF-ResNet's pooled features
+    uint8_t* PIDX = nullptr;                   // NF-ResNet stem max pool: window index of every pooled element
+    AT* COL = nullptr;                         // NF-ResNet stem columns [n*ho*wo, 49*8] (see stem_col)
     std::vector<VitActs> vb;
     AT* X0;
     AT *Cs[3], *As[3];
@@ -367,12 +393,29 @@ struct Eng : mdd_engine {
         lpd.push_back(d);
       }
     } else {
+    // the two walkers: NFNet (deep_quad stem, squeeze-excite, conv2b, final conv) and the plain residual one of
+    // NF-ResNet (7x7_pool stem, none of those three); other mixes of the switches have no walker
+    const bool nfnet_like = !nf.stem_pool && nf.se && nf.conv2b && nf.final_conv && !nf.classes;
+    const bool plain_res = nf.stem_pool && !nf.se && !nf.conv2b && !nf.final_conv;
+    CHECK_ARG(nfnet_like || plain_res, "internal: unsupported NormFreeNet topology");
+    ract = nf.relu ? 3 : 0;
+    int prev = 3, h = S;
+    if (nf.stem_pool) {
+      // stem '7x7_pool': conv 7x7 / 2 (no activation), MaxPool2d(3, 2, padding=1)
+      stem[0] = add_conv("model.stem.conv", 3, nf.stem_chs, 7, 2, 1, h);
+      stem[1] = stem[2] = stem[3] = -1;
+      const ConvL& L0 = convs[stem[0]];
+      stem_col = L0;
+      stem_col.k = 1; stem_col.stride = 1; stem_col.pad = 0; stem_col.hin = L0.hout;
+      stem_col.cin = stem_col.cin_pad = L0.k * L0.k * L0.cin_pad;
+      h = maxpool3s2_out(L0.hout); prev = nf.stem_chs;
+    } else {
     // stem 'deep_quad': 3x3 convs, channels (sc/8, sc/4, sc/2, sc), strides (2,1,1,2)
     int sc = nf.stem_chs, chs[4] = {sc / 8, sc / 4, sc / 2, sc}, strides[4] = {2, 1, 1, 2};
-    int prev = 3, h = S;
     for (int i = 0; i < 4; ++i) {
       stem[i] = add_conv("model.stem.conv" + std::to_string(i + 1), prev, chs[i], 3, strides[i], 1, h);
       h = convs[stem[i]].hout; prev = chs[i];
+    }
     }
     xh.push_back(h); xc.push_back(prev);
     double expected_var = 1.0;
@@ -391,14 +434,17 @@ struct Eng : mdd_engine {
         if (prev != out || stride != 1) B.ds = add_conv(pre + ".downsample.conv", prev, out, 1, 1, 1, hout);
         B.c1 = add_conv(pre + ".conv1", prev, mid, 1, 1, 1, h);
         B.c2 = add_conv(pre + ".conv2", mid, mid, 3, stride, groups, h);
-        B.c2b = add_conv(pre + ".conv2b", mid, mid, 3, 1, groups, hout);
+        B.c2b = nf.conv2b ? add_conv(pre + ".conv2b", mid, mid, 3, 1, groups, hout) : -1;
         B.c3 = add_conv(pre + ".conv3", mid, out, 1, 1, 1, hout);
         CHECK_ARG(convs[B.c2].hout == hout, "internal: spatial plan");
-        B.se.c = out; B.se.rd = make_divisible(out * nf.se_rd_ratio, 8, 0.0);
+        B.se.c = out; B.se.rd = 0; B.se.off_w1 = B.se.off_b1 = B.se.off_w2 = B.se.off_b2 = -1;
+        if (nf.se) {
+        B.se.rd = make_divisible(out * nf.se_rd_ratio, 8, 0.0);
         B.se.off_w1 = add_param(pimg, pre + ".attn_last.fc1.weight", {B.se.rd, out, 1, 1});
         B.se.off_b1 = add_param(pimg, pre + ".attn_last.fc1.bias", {B.se.rd});
         B.se.off_w2 = add_param(pimg, pre + ".attn_last.fc2.weight", {out, B.se.rd, 1, 1});
         B.se.off_b2 = add_param(pimg, pre + ".attn_last.fc2.bias", {out});
+        }
         B.hout = hout;
         blks.push_back(B);
         if (bi == 0) expected_var = 1.0;
@@ -407,8 +453,18 @@ struct Eng : mdd_engine {
         xh.push_back(h); xc.push_back(prev);
       }
     }
+    if (nf.final_conv) {
     feat = (int)(nf.channels[3] * nf.feat_mult);
     fin = add_conv("model.final_conv", prev, feat, 1, 1, 1, h);
+    } else {
+      feat = prev; fin = -1;
+    }
+    fpool = feat;
+    if (nf.classes > 0) {   // timm ClassifierHead: global average pool, then head.fc
+      off_hw = add_param(pimg, "model.head.fc.weight", {nf.classes, fpool});
+      off_hb = add_param(pimg, "model.head.fc.bias", {nf.classes});
+      feat = nf.classes;
+    }
     P_img = off;
     }   // NFNet topology
     CHECK_ARG(feat <= 4096, "feature dim > 4096 unsupported by the contrastive head kernel");
@@ -482,8 +538,57 @@ struct Eng : mdd_engine {
     plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
     plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
   }
+  // NF-ResNet (7x7_pool stem, no squeeze-excite / conv2b / final conv): stem conv output + pooled stream + window index,
+  // per block {C1, A1, C2, A2, C3} and their gradients, the pooled features in front of the classifier
+  void plan_set_res(ActSet& s, int slot) {
+    const int nb = (int)blks.size();
+    const int64_t n = N;
+    const ConvL& L0 = convs[stem[0]];
+    // the image has no tangent and the tangent passes read the window index and the columns of the primal slot:
+    // the tangent set (slot -1) has no input, columns or index of its own
+    s.X0 = s.COL = nullptr; s.PIDX = nullptr;
+    if (slot >= 0) plan(&s.X0, n * S * S * 8, "IN", slot);
+    const int64_t e0 = n * L0.hout * L0.hout * L0.cout;
+    plan(&s.Cs[0], e0, "stem.C0", slot); plan(&s.CsB[0], e0, "stem.CB0", slot);
+    if (slot >= 0) {
+      plan(&s.PIDX, n * xh[0] * xh[0] * xc[0], nullptr, slot);
+      plan(&s.COL, n * L0.hout * L0.hout * stem_col.cin_pad, nullptr, slot);
+    }
+    plan(&s.X0B, n * S * S * 8, "INB", slot);
+    s.X.resize(nb + 1); s.A.resize(nb + 1); s.XB.resize(nb + 1); s.blk.resize(nb);
+    for (int b = 0; b <= nb; ++b) {
+      int64_t e = n * xh[b] * xh[b] * xc[b];
+      plan(&s.X[b], e, ("X" + std::to_string(b)).c_str(), slot);
+      plan(&s.XB[b], e, ("XB" + std::to_string(b)).c_str(), slot);
+      if (b < nb) plan(&s.A[b], e, ("A" + std::to_string(b)).c_str(), slot); else s.A[b] = nullptr;
+    }
+    for (int b = 0; b < nb; ++b) {
+      const Blk& B = blks[b]; BlockActs& a = s.blk[b];
+      memset(&a, 0, sizeof a);
+      std::string p = "b" + std::to_string(b) + ".";
+      int64_t ein = n * B.hin * B.hin, eout = n * B.hout * B.hout;
+      if (B.ds >= 0 && B.stride == 2) plan(&a.P, eout * B.cin, (p + "P").c_str(), slot);
+      if (B.ds >= 0) plan(&a.SC, eout * B.cout, (p + "SC").c_str(), slot);
+      plan(&a.C1, ein * B.mid, (p + "C1").c_str(), slot);   plan(&a.A1, ein * B.mid, (p + "A1").c_str(), slot);
+      plan(&a.C2, eout * B.mid, (p + "C2").c_str(), slot);  plan(&a.A2, eout * B.mid, (p + "A2").c_str(), slot);
+      plan(&a.C3, eout * B.cout, (p + "C3").c_str(), slot);
+      plan(&a.C3B, eout * B.cout, (p + "C3B").c_str(), slot);
+      plan(&a.A2B, eout * B.mid, (p + "A2B").c_str(), slot);   plan(&a.C2B, eout * B.mid, (p + "C2B").c_str(), slot);
+      plan(&a.A1B, ein * B.mid, (p + "A1B").c_str(), slot);    plan(&a.C1B, ein * B.mid, (p + "C1B").c_str(), slot);
+      plan(&a.AinB, ein * B.cin, (p + "AinB").c_str(), slot);
+    }
+    s.CF = s.CFB = nullptr;
+    if (nf.classes > 0) { plan(&s.hin, n * fpool, "pooled", slot); plan(&s.hinB, n * fpool, "pooledB", slot); }
+    plan(&s.y, n * feat, "y", slot); plan(&s.yB, n * feat, "yB", slot);
+    plan(&s.dwf, packed_total, "dwf", slot);
+    plan(&s.tx, n * Dt, "tx", slot); plan(&s.tp, n * feat, "tp", slot); plan(&s.tg, n * feat, "tg", slot);
+    plan(&s.tf, n * feat, "tf", slot); plan(&s.tr, n * feat, "tr", slot); plan(&s.ty, n * feat, "ty", slot);
+    plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
+    plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
+  }
   void plan_set(ActSet& s, int slot) {
     if (is_vit) { plan_set_vit(s, slot); return; }
+    if (nf.stem_pool) { plan_set_res(s, slot); return; }
     int nb = (int)blks.size();
     auto nm = [&](const std::string& n) { return n; };
     int64_t n = N;
@@ -562,7 +667,7 @@ struct Eng : mdd_engine {
     plan(&ln_stats, (int64_t)N * 4, nullptr, -2);
     // squeeze-excite shortcut operands, per block (se_prep): W13 = W1 W3_hat [rd, mid], b13 = W1 b3 + b1, tangents
     se13.resize(blks.size());
-    for (size_t b = 0; b < blks.size(); ++b) {
+    for (size_t b = 0; b < blks.size() && nf.se; ++b) {
       const int64_t rm = (int64_t)blks[b].se.rd * blks[b].mid;
       plan(&se13[b].W, rm, nullptr, -2); plan(&se13[b].W_t, rm, nullptr, -2);
       plan(&se13[b].b, blks[b].se.rd, nullptr, -2); plan(&se13[b].b_t, blks[b].se.rd, nullptr, -2);
@@ -1199,6 +1304,151 @@ struct Eng : mdd_engine {
   }
 #undef VIT_RC
 
+  // ================================================================== NF-ResNet image encoder (timm nf_resnet50)
+  // stem conv 7x7 / 2 -> max pool 3x3 / 2 -> blocks {a = beta*relu(x); shortcut = x or downsample(a);
+  // x' = alpha*conv3(relu(conv2(relu(conv1(a))))) + shortcut} -> relu -> global average pool -> classifier.
+  // The activations of conv1 / conv2 come out of their contractions' ReLU epilogues (and, backward, their chain rule
+  // out of the data gradients' epilogues, ConvEpi::act = 3); the residual sum and the next block's pre-activation are
+  // one elementwise pass (launch_resid_relu), the max pool keeps a one-byte window index for its backward.
+  int res_forward(bool T, int slot, const float* th, const float* th_t, const float* image, const int64_t* idx,
+                  float* feat_out, hipStream_t st) {
+    ActSet& P = sets[slot]; ActSet& Q = tn;
+    const int nb = (int)blks.size();
+    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
+    launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
+                          wf_t, wt_t, st);
+    const ConvL& L0 = convs[stem[0]];
+    if (!T) {
+      launch_img_gather_nhwc<AT>(P.X0, image, idx, N, 3, S, S, 8, st);
+      launch_im2col<AT>(P.COL, P.X0, N, S, S, L0.cin_pad, L0.k, L0.stride, L0.pad, L0.hout, L0.hout, st);
+    }
+    conv_fwd(T, stem_col, P.COL, nullptr, P.Cs[0], Q.Cs[0], nullptr, nullptr, 1.f, th, th_t, st);
+    if (!T)
+      launch_maxpool3s2<AT>(P.X[0], P.PIDX, P.A[0], P.Cs[0], blks[0].beta, N, L0.hout, L0.hout, L0.cout, st);
+    else
+      launch_maxpool3s2_t<AT>(Q.X[0], Q.A[0], P.X[0], P.PIDX, Q.Cs[0], blks[0].beta, N, L0.hout, L0.hout, L0.cout, st);
+    for (int b = 0; b < nb; ++b) {
+      const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
+      const AT *a = P.A[b], *a_t = Q.A[b];
+      const AT *sc = P.X[b], *sc_t = Q.X[b];
+      bool sc_forked = false;
+      if (B.ds >= 0) {
+        // the shortcut (avg-pool + 1x1 conv) only meets the residual branch at the residual sum: side stream
+        hipStream_t ss = st;
+        if (use_side && MDD_FWD_SHORTCUT_SIDE) { fork(st); ss = side; sc_forked = true; }
+        const AT *din = a, *din_t = a_t;
+        if (B.stride == 2) {
+          launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
+          din = pa.P; din_t = qa.P;
+        }
+        conv_fwd(T, convs[B.ds], din, din_t, pa.SC, qa.SC, nullptr, nullptr, 1.f, th, th_t, ss);
+        sc = pa.SC; sc_t = qa.SC;
+      }
+      conv_fwd(T, convs[B.c1], a, a_t, pa.C1, qa.C1, pa.A1, qa.A1, 1.f, th, th_t, st, ract);
+      conv_fwd(T, convs[B.c2], pa.A1, qa.A1, pa.C2, qa.C2, pa.A2, qa.A2, 1.f, th, th_t, st, ract);
+      conv_fwd(T, convs[B.c3], pa.A2, qa.A2, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
+      if (sc_forked) join(st);
+      const bool lastb = b == nb - 1;
+      launch_resid_relu<AT>(pa.C3, T ? qa.C3 : nullptr, sc, T ? sc_t : nullptr, P.X[b + 1], T ? Q.X[b + 1] : nullptr,
+                            lastb ? nullptr : P.A[b + 1], (T && !lastb) ? Q.A[b + 1] : nullptr, nf.alpha,
+                            lastb ? 1.f : blks[b + 1].beta, (int64_t)N * B.hout * B.hout * B.cout, st);
+    }
+    // final_act (ReLU, no beta) + global average pool, then the classifier (small-batch fp32 linear)
+    const int hwf = xh[nb] * xh[nb];
+    if (nf.classes > 0) {
+      launch_final_pool<AT>(P.hin, T ? Q.hin : nullptr, P.X[nb], T ? Q.X[nb] : nullptr, N, hwf, fpool, st, nf.relu != 0);
+      launch_linear_fwd(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_hw, tp(th_t + off_hw),
+                        th + off_hb, tp(th_t + off_hb), N, fpool, nf.classes, 0, lin_main, st);
+    } else {
+      launch_final_pool<AT>(P.y, T ? feat_out : nullptr, P.X[nb], T ? Q.X[nb] : nullptr, N, hwf, feat, st, nf.relu != 0);
+    }
+    if (!T && feat_out && feat_out != P.y)
+      HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    POST_WALK("res_forward");
+    return 0;
+  }
+  int res_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in, const float* ybar_t_in,
+                   float* gout, float* dimage, const int64_t* idx, const float* coef, float mul, bool repack, bool stash,
+                   hipStream_t st) {
+    ActSet& P = sets[slot]; ActSet& Q = tn;
+    ActSet& O = (!T && !stash) ? tn : P;  // where primal backward signals are written
+    const int nb = (int)blks.size();
+    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
+    if (repack)
+      launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
+                            wf_t, wt_t, st);
+    float* dw = O.dwf; float* dw_t = Q.dwf;
+    HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
+    if (!T && ybar_in != O.yB)
+      HIP_CHECK_RET(hipMemcpyAsync(O.yB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    const int hwf = xh[nb] * xh[nb];
+    if (nf.classes > 0) {
+      launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N,
+                          fpool, nf.classes, lin_main, st);
+      launch_linear_dgrad(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_hw, tp(th_t + off_hw),
+                          nullptr, N, fpool, nf.classes, lin_main, st);
+      launch_final_pool_bwd<AT>(O.XB[nb], T ? Q.XB[nb] : nullptr, O.hinB, T ? Q.hinB : nullptr, P.X[nb],
+                                T ? Q.X[nb] : nullptr, N, hwf, fpool, st, nf.relu != 0);
+    } else {
+      launch_final_pool_bwd<AT>(O.XB[nb], T ? Q.XB[nb] : nullptr, O.yB, T ? ybar_t_in : nullptr, P.X[nb],
+                                T ? Q.X[nb] : nullptr, N, hwf, feat, st, nf.relu != 0);
+    }
+    for (int b = nb - 1; b >= 0; --b) {
+      const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
+      BlockActs& oa = O.blk[b];
+      const AT *xb = O.XB[b + 1], *xb_t = Q.XB[b + 1];
+      const int64_t eout = (int64_t)N * B.hout * B.hout;
+      // x' = alpha*c3 + shortcut: conv3's output gradient is alpha times the block output's
+      launch_scale_act<AT>(T ? qa.C3B : oa.C3B, T ? xb_t : xb, nf.alpha, eout * B.cout, st);
+      conv_bwd_w(T, convs[B.c3], oa.C3B, qa.C3B, pa.A2, qa.A2, dw, dw_t, gout, st);
+      flush_w(st);
+      ConvEpi e3 = epi_act(T, oa.A2B, oa.C2B, qa.C2B, pa.C2, qa.C2, 1.f, nullptr, nullptr);
+      e3.act = ract;
+      conv_bwd_d(T, convs[B.c3], oa.C3B, qa.C3B, e3, st);
+      conv_bwd_w(T, convs[B.c2], oa.C2B, qa.C2B, pa.A1, qa.A1, dw, dw_t, gout, st);
+      ConvEpi e2 = epi_act(T, oa.A1B, oa.C1B, qa.C1B, pa.C1, qa.C1, 1.f, nullptr, nullptr);
+      e2.act = ract;
+      conv_bwd_d(T, convs[B.c2], oa.C2B, qa.C2B, e2, st);
+      conv_bwd_w(T, convs[B.c1], oa.C1B, qa.C1B, P.A[b], Q.A[b], dw, dw_t, gout, st);
+      // shortcut branch
+      const AT* add1 = nullptr;
+      if (B.ds >= 0) {
+        const AT* dsin = B.stride == 2 ? pa.P : P.A[b];
+        const AT* dsin_t = B.stride == 2 ? qa.P : Q.A[b];
+        conv_bwd_w(T, convs[B.ds], xb, xb_t, dsin, dsin_t, dw, dw_t, gout, st);
+        conv_bwd_d(T, convs[B.ds], xb, xb_t, epi_lin(dsS, nullptr), st);
+        if (B.stride == 2) {
+          launch_avgpool2_bwd<AT>(dsF, dsS, N, B.hin, B.hin, B.cin, 2, st);
+          add1 = dsF;
+        } else {
+          add1 = dsS;
+        }
+      }
+      // conv1 dgrad + pre-activation chain rule + identity shortcut:  XB[b] = beta*1[X[b] > 0]*Abar (+ XB[b+1])
+      ConvEpi e1 = epi_act(T, oa.AinB, O.XB[b], Q.XB[b], P.X[b], Q.X[b], B.beta, add1,
+                           B.ds >= 0 ? nullptr : (T ? xb_t : xb));
+      e1.act = ract;
+      conv_bwd_d(T, convs[B.c1], oa.C1B, qa.C1B, e1, st);
+      if (b == 0) flush_w(st);
+    }
+    // stem: max-pool backward (gather through the window index), then the 7x7 conv's weight and image gradients
+    const ConvL& L0 = convs[stem[0]];
+    launch_maxpool3s2_bwd<AT>(T ? Q.CsB[0] : O.CsB[0], T ? Q.XB[0] : O.XB[0], P.PIDX, N, L0.hout, L0.hout, L0.cout, st);
+    if (dimage) {
+      // no pixel-parallel kernel for the 7x7 stem: stride-2 transposed implicit GEMM, then the NCHW scatter
+      AT* x0b = T ? Q.X0B : O.X0B;
+      conv_bwd_d(T, L0, O.CsB[0], Q.CsB[0], epi_lin(x0b, nullptr), st);
+      launch_img_scatter_grad<AT>(dimage, x0b, idx, coef, mul, N, 3, S, S, 8, st);
+    }
+    conv_bwd_w(T, stem_col, O.CsB[0], Q.CsB[0], P.COL, nullptr, dw, dw_t, gout, st);
+    flush_w(st, MAIN_TAIL);
+    join(st);
+    launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw,
+                       T ? dw_t : nullptr, gout, st);
+    POST_WALK("res_backward");
+    return 0;
+  }
+
   // ------------------------------------------------------------------ image encoder: F / T-fwd
   int img_forward(bool T, int slot, const float* th, const float* th_t, const float* image,
                   const int64_t* idx, float* feat_out, hipStream_t st) override {
@@ -1207,6 +1457,7 @@ struct Eng : mdd_engine {
     CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
     select_prec(T, false);
     if (is_vit) return vit_forward(T, slot, th, th_t, image, idx, feat_out, st);
+    if (nf.stem_pool) return res_forward(T, slot, th, th_t, image, idx, feat_out, st);
     ActSet& P = sets[slot]; ActSet& Q = tn;
     int nb = (int)blks.size();
     launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
@@ -1315,6 +1566,7 @@ struct Eng : mdd_engine {
     CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
     select_prec(T, true);
     if (is_vit) return vit_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+    if (nf.stem_pool) return res_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
     ActSet& P = sets[slot]; ActSet& Q = tn;
     ActSet& O = (!T && !stash) ? tn : P;  // where primal backward signals are written
     int nb = (int)blks.size();
@@ -1961,6 +2213,28 @@ int mdd_op_conv2d_wgrad2(int dtype, int nimg, int hin, int win, int cin, int cou
     launch_conv_wgrad<bf16>(g, (const bf16*)dy1, (const bf16*)x1, (const bf16*)dy2, (const bf16*)x2, dw, db, ws,
                             (int64_t)ws_floats, nullptr, (hipStream_t)stream);
   POST_LAUNCH("op_conv2d_wgrad2");
+  return 0;
+}
+
+int mdd_op_maxpool2d_3s2(int dtype, int mode, int n, int h, int w, int c, const void* x, void* y, void* idx,
+                         void* stream) {
+  CHECK_ARG(x && y && idx, "null pointer");
+  CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0, "empty problem");
+  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype must be MDD_DTYPE_F32 or MDD_DTYPE_BF16");
+  CHECK_ARG(mode >= 0 && mode <= 2, "mode must be 0 (forward), 1 (tangent) or 2 (backward)");
+  CHECK_ARG(c % (dtype == MDD_DTYPE_F32 ? 4 : 8) == 0, "channels must be a multiple of the 16-byte chunk");
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* ix = (uint8_t*)idx;
+  if (dtype == MDD_DTYPE_F32) {
+    if (mode == 0) launch_maxpool3s2<float>((float*)y, ix, nullptr, (const float*)x, 1.f, n, h, w, c, st);
+    else if (mode == 1) launch_maxpool3s2_t<float>((float*)y, nullptr, nullptr, ix, (const float*)x, 1.f, n, h, w, c, st);
+    else launch_maxpool3s2_bwd<float>((float*)y, (const float*)x, ix, n, h, w, c, st);
+  } else {
+    if (mode == 0) launch_maxpool3s2<bf16>((bf16*)y, ix, nullptr, (const bf16*)x, 1.f, n, h, w, c, st);
+    else if (mode == 1) launch_maxpool3s2_t<bf16>((bf16*)y, nullptr, nullptr, ix, (const bf16*)x, 1.f, n, h, w, c, st);
+    else launch_maxpool3s2_bwd<bf16>((bf16*)y, (const bf16*)x, ix, n, h, w, c, st);
+  }
+  POST_LAUNCH("op_maxpool2d_3s2");
   return 0;
 }
 

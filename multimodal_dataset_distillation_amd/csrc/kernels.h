@@ -68,7 +68,7 @@ struct ConvEpi {
   const float* ib_t;
   float ib_mul;
   int ib_hw;
-  int act;                // activation of the fused chain rule: 0 SiLU, 1 exact GELU (conv_gemm_supports_gelu)
+  int act;                // activation of the fused chain rule: 0 SiLU, 1 exact GELU (conv_gemm_supports_gelu), 3 ReLU
 };
 enum {
   EPI_FWD = 0,        // c = acc + bias ; out_raw = c ; out_act = beta*silu(c)
@@ -92,6 +92,11 @@ template <class AT>
 void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
                       const ConvEpi& ep, hipStream_t st);
 bool conv_gemm_supports_gelu(const ConvGeom& g);
+// ConvEpi::act == 3 (ReLU) with an activation output: the ReLU instances (conv_gemm_relu.hip); launch_conv_gemm
+// forwards such launches itself
+template <class AT>
+void launch_conv_gemm_relu(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
+                           const ConvEpi& ep, hipStream_t st);
 // the 256 x 256 pipelined kernels (k_gemm_pipe, k_wgrad_pipe) may be switched off at run time: the parity tests compare
 // an iteration with and without them (mdd_set_pipe_kernels)
 bool pipe_kernels_enabled();
@@ -159,14 +164,40 @@ template <class AT>
 void launch_se_apply_bwd(AT* c3bar, AT* c3bar_t, const AT* xbar, const AT* xbar_t,
                          const float* gate, const float* gate_t, const float* pbar,
                          const float* pbar_t, float ga, int n, int hw, int c, hipStream_t st);
-// y[n,f] = mean_hw silu(cf)
+// y[n,f] = mean_hw silu(cf)   (relu = true: mean_hw relu(cf), NF-ResNet)
 template <class AT>
 void launch_final_pool(float* y, float* y_t, const AT* cf, const AT* cf_t, int n, int hw, int c,
-                       hipStream_t st);
-// cfbar = ybar/hw * dsilu(cf)
+                       hipStream_t st, bool relu = false);
+// cfbar = ybar/hw * dsilu(cf)   (relu = true: ybar/hw * 1[cf > 0])
 template <class AT>
 void launch_final_pool_bwd(AT* cfbar, AT* cfbar_t, const float* ybar, const float* ybar_t,
-                           const AT* cf, const AT* cf_t, int n, int hw, int c, hipStream_t st);
+                           const AT* cf, const AT* cf_t, int n, int hw, int c, hipStream_t st, bool relu = false);
+
+// ---------------------------------------------------------------- nfres.hip (NF-ResNet image path)
+// MaxPool2d(3, 2, padding=1) on NHWC [n, h, w, c]: pooled [n, ho, wo, c] (ho = (h-1)/2+1), one-byte window index
+// (ky*3+kx of the first maximum) per element, act (optional) = beta*relu(pooled)
+int maxpool3s2_out(int h);
+template <class AT>
+void launch_maxpool3s2(AT* out, uint8_t* widx, AT* act, const AT* in, float beta, int n, int h, int w, int c,
+                       hipStream_t st);
+// tangent: out_t = in_t at the stored index; act_t (optional) = beta*1[pooled > 0]*out_t
+template <class AT>
+void launch_maxpool3s2_t(AT* out_t, AT* act_t, const AT* pooled, const uint8_t* widx, const AT* in_t, float beta, int n,
+                         int h, int w, int c, hipStream_t st);
+// backward (and, applied to the tangent of dout, tangent backward): din = gather of dout through the index
+template <class AT>
+void launch_maxpool3s2_bwd(AT* din, const AT* dout, const uint8_t* widx, int n, int h, int w, int c, hipStream_t st);
+// X' = alpha*C3 + SC ; A' = beta*relu(X')  (ao / ao_t may be null; tangent when c3_t is non-null: writes tangents only)
+template <class AT>
+void launch_resid_relu(const AT* c3, const AT* c3_t, const AT* sc, const AT* sc_t, AT* xo, AT* xo_t, AT* ao, AT* ao_t,
+                       float alpha, float beta, int64_t elems, hipStream_t st);
+// columns of a k x k conv on NHWC [n, h, w, cpad]: col [n*ho*wo, k*k*cpad] in the packed forward weight's K order
+template <class AT>
+void launch_im2col(AT* col, const AT* in, int n, int h, int w, int cpad, int k, int stride, int pad, int ho, int wo,
+                   hipStream_t st);
+// out = alpha*in  (elems a multiple of the 16-byte chunk)
+template <class AT>
+void launch_scale_act(AT* out, const AT* in, float alpha, int64_t elems, hipStream_t st);
 
 // ---------------------------------------------------------------- linear.hip (fp32, small M)
 // Split-K scratch of the small-M SGEMM: per-tile accumulators, bias-gradient row sums and arrival

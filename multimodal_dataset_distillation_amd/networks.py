@@ -24,10 +24,12 @@ from . import functional as Fn
 # WITHOUT num_classes=0 (:668): the model keeps timm's 1000-way head (5,717,416 parameters, 1000-d features into the
 # projection, networks.py:819) = 'vit_tiny16_cls' here, so reference-format 'vit' expert buffers flatten to P_img.
 # 'vit_tiny16' (headless, 192-d class token) and 'vit_b16' (BASELINE configs[4]'s ViT-B/16; the reference's 'clip' is
-# ViT-B/32 through the clip package) are build-defined.
+# ViT-B/32 through the clip package) are build-defined.  'nf_resnet50' is timm.create_model('nf_resnet50', pretrained=True)
+# (networks.py:669-670), also with its 1000-way head: 1000-d features; 'nf_resnet_tiny' is its build-defined miniature.
 VARIANTS = {"nfnet": "nfnet_l0", "nfnet_l0": "nfnet_l0", "nfnet_l1": "nfnet_l1",
             "nfnet_tiny": "nfnet_tiny", "vit": "vit_tiny16_cls", "vit_tiny16_cls": "vit_tiny16_cls",
-            "vit_tiny16": "vit_tiny16", "vit_b16": "vit_b16", "vit_micro": "vit_micro", "vit_micro_cls": "vit_micro_cls"}
+            "vit_tiny16": "vit_tiny16", "vit_b16": "vit_b16", "vit_micro": "vit_micro", "vit_micro_cls": "vit_micro_cls",
+            "nf_resnet50": "nf_resnet50", "nf_resnet_tiny": "nf_resnet_tiny"}
 
 _ENGINES = {}
 
@@ -70,8 +72,9 @@ def _attach(root, dotted, param):
 
 def init_image_params(table, generator=None, trained_like=False):
     """timm NormFreeNet init: kaiming_normal_(fan_in, linear) conv weights, zero bias, gain 1 (conv3:
-    0).  trained_like=True perturbs gains/biases the way oracle/nfnet_ref.randomize_like_trained
-    does (synthetic expert snapshots; default init zeroes most of the theta-gradient)."""
+    0); a classifier (NF-ResNet's head.fc): normal(0, 0.01) weight, zero bias.  trained_like=True perturbs
+    gains/biases the way oracle/nfnet_ref.randomize_like_trained does (synthetic expert snapshots; default
+    init zeroes most of the theta-gradient)."""
     out = []
     if any(name == "model.cls_token" for name, _, _ in table):
         # timm VisionTransformer init: trunc_normal(0.02) linear weights and position embedding, zero biases, unit
@@ -93,7 +96,9 @@ def init_image_params(table, generator=None, trained_like=False):
             out.append(t)
         return out
     for name, shape, _ in table:
-        if name.endswith(".weight"):
+        if name.endswith(".weight") and len(shape) == 2:
+            t = 0.01 * torch.randn(shape, generator=generator)
+        elif name.endswith(".weight"):
             fan_in = int(shape[1] * shape[2] * shape[3])
             t = torch.randn(shape, generator=generator) / math.sqrt(fan_in)
         elif name.endswith(".gain"):
