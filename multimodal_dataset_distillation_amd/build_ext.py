@@ -1,4 +1,4 @@
-"""Builds csrc/*.hip + engine.cpp into the in-tree C-ABI shared library libmdd_hip.so for gfx950.
+"""Builds csrc/*.hip (the engine is csrc/engine.hip) into the in-tree C-ABI shared library libmdd_hip.so for gfx950.
 
 `python -m multimodal_dataset_distillation_amd.build_ext` (or `__graft_entry__.build()`).
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels with gpurun snapshots.
@@ -18,7 +18,7 @@ SOURCES = ["flat_ops.hip", "ws.hip", "elementwise.hip", "linear.hip", "head.hip"
            "nfres.hip", "engine.hip"]
 # sources that include another source file: rebuilt when it changes
 INCLUDES = {"conv_gemm_relu.hip": ["conv_gemm.hip"]}
-HEADERS = ["common.h", "kernels.h", "engine.h", "conv_gemm_epilogue.inc", os.path.join("..", "..", "include", "mdd_hip.h")]
+HEADERS = ["common.h", "kernels.h", "conv_gemm_epilogue.inc", os.path.join("..", "..", "include", "mdd_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result",
          "-I", os.path.join(HERE, "..", "include")]
 

@@ -29,28 +29,8 @@
 #ifndef MDD_EPI_UNROLL
 #define MDD_EPI_UNROLL 4
 #endif
-#ifndef MDD_BIG_TILE
-#define MDD_BIG_TILE 0
-#endif
-#ifndef MDD_SINGLE_BUF
-#define MDD_SINGLE_BUF 1
-#endif
-#ifndef MDD_FRAG_PREFETCH
-#define MDD_FRAG_PREFETCH 1
-#endif
 #ifndef MDD_MIN_WAVES
 #define MDD_MIN_WAVES 3
-#endif
-
-#ifndef MDD_PIPE_EPI_HOIST
-#define MDD_PIPE_EPI_HOIST 1  // k_gemm_pipe: first group of stash loads of a 32-row block issued before its LDS transposition
-#endif
-#ifndef MDD_EPI_WAVE_SYNC
-#define MDD_EPI_WAVE_SYNC 0   // k_conv_gemm: wave-level ordering instead of block barriers between the 32-row blocks of the epilogue
-#endif
-#ifndef MDD_SPLIT_3TERM
-#define MDD_SPLIT_3TERM 1   // bf16x2 K loop of the 2x2-wave instances: hh + hl + lh on register-regrouped chunk pairs
-                            // (0: hh + ll + hl + lh everywhere)
 #endif
 
 namespace {
@@ -212,9 +192,8 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
   constexpr int RA = BM / 32, RB = BN / 32;
   typedef typename MmaSel<AT, PREC>::type MT;
   constexpr int KE = MT::KE, CE = MT::CE;
-  constexpr bool EPI_WAVE_SYNC = MDD_EPI_WAVE_SYNC != 0;
+  constexpr bool EPI_WAVE_SYNC = false;   // block barriers between the 32-row blocks of the epilogue
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NBUF = MDD_SINGLE_BUF ? 1 : 2;   // LDS stages (registers hold the slab in flight)
 
   const ConvGeom& G = p.g;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -325,9 +304,7 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
     boff[i] = ((grp * G.nc + n) * ktot_w + (MODE == 2 ? 0 : cj * CE)) * ESZ;
   }
   // LDS byte addresses.  Rows 32 apart share the swizzle, so the i / j sub-tiles are reached with
-  // immediate offsets (i * 4096) from ONE register per q.  (With MDD_SINGLE_BUF=0 a second LDS stage is
-  // toggled by XOR-ing one bit into these few registers per K-step: buffer strides are powers of two.)
-  constexpr int ABUF = NBUF == 2 ? BM * 128 : 0, BBUF = NBUF == 2 ? BN * 128 : 0;
+  // immediate offsets (i * 4096) from ONE register per q.
   // MODE 4 (3x3, stride 1, "same" size, one 128-byte channel row per pixel and group): the A operand of
   // ALL nine taps is one contiguous slab of the NHWC tensor -- source pixel = m + (ty-1)*W + (tx-1) for every
   // tap that lies inside the image -- so the block loads pixels [m0-W-1, m0+BM+W] ONCE into LDS and the
@@ -337,7 +314,7 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
   // times through L1 with one latency-bound round trip per tap.
   const int slab_pad = e_wo + 1;
   const int slab_pix = BM + 2 * e_wo + 2;
-  const int BBASE = MODE == 4 ? (slab_pix + 1) * 128 : NBUF * BM * 128;
+  const int BBASE = MODE == 4 ? (slab_pix + 1) * 128 : BM * 128;
   const int l31 = lane & 31, lh = lane >> 5;
   int rdA[4], rdB[4];
 #pragma unroll
@@ -345,7 +322,7 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
     rdA[q] = lds_off(wm * TM * 32 + l31, 2 * q + lh);
     rdB[q] = BBASE + lds_off(wn * TN * 32 + l31, 2 * q + lh);
   }
-  int wrA = lds_off(r0, cj), wrB = BBASE + lds_off(r0, cj);   // stage 0 goes to buffer 0
+  const int wrA = lds_off(r0, cj), wrB = BBASE + lds_off(r0, cj);
   // MODE 4: slab pixel of this lane's fragment rows at the centre tap, and their tap-validity masks
   int sp0[MODE == 4 ? TM : 1];
   unsigned tapf[MODE == 4 ? TM : 1];
@@ -465,7 +442,6 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
 #pragma unroll
       for (int i = 0; i < RB; ++i)
         *(u32x4*)(smem + wrB + t * (BN * 128) + i * 4096) = MT::stage(S.rb[t * RB + i], hi_only);
-    wrA ^= ABUF; wrB ^= BBUF;
   };
   // MODE 4: pixels [m0 - W - 1, m0 + BM + W] of this group's channel row -> LDS, eight 16-byte loads per
   // thread in flight at a time; pixels before / after the tensor read zeros (only masked taps touch them)
@@ -515,7 +491,7 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
         }
       }
     } else
-    if constexpr (MDD_FRAG_PREFETCH && sizeof(AT) == 2 && MODE == 0) {
+    if constexpr (sizeof(AT) == 2 && MODE == 0) {
     // the LDS fragments of K-slice q+1 are fetched before the MFMAs of slice q are issued (the scheduling
     // barriers keep the compiler from sinking the fetch back next to its use): +11..14 % on the long-K,
     // single-round shapes in tools/micro/gemm_core.hip, neutral elsewhere
@@ -539,7 +515,7 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
         for (int j = 0; j < TN; ++j) MT::step(af[q & 1][i], bf[q & 1][j], acc[i][j]);
       __builtin_amdgcn_sched_barrier(0);
     }
-    } else if constexpr (PREC >= 1 && MDD_SPLIT_3TERM && WGM == 2) {
+    } else if constexpr (PREC >= 1 && WGM == 2) {
     // bf16x2, 2x2-wave instances: the fragments of two K-slices at once, three MFMAs per pair (step2).  The
     // 4x1-wave instances keep one slice at a time: the second fragment set does not fit their 168 registers
     // (measured: 256x64 class 144 -> 191 ms per C2 iteration with it, 128x128 class 190 -> 170 ms).
@@ -572,8 +548,6 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
         for (int j = 0; j < TN; ++j) MT::step(af[i], bf[j], acc[i][j]);
     }
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { rdA[q] ^= ABUF; rdB[q] ^= BBUF; }
   };
   if constexpr (MODE == 4) {
     if (tid < 8) *(u32x4*)(smem + slab_pix * 128 + tid * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -591,7 +565,7 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
       }
     }
     compute(kt);
-    if (NBUF == 1) __syncthreads();      // everyone is done reading the slab before it is replaced
+    __syncthreads();      // everyone is done reading the slab before it is replaced
     if (kt + 1 < nk) store_tile(s0);
     __syncthreads();
   }
@@ -616,17 +590,6 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
 #ifndef MDD_PIPE_MIN
 #define MDD_PIPE_MIN 768     // narrowest layer (K and output channels) taken by k_gemm_pipe: the ViT linears; NFNet-l0's 512- and 1536-wide layers ran 0.6 % slower per iteration with it
 #endif
-#ifndef MDD_PIPE_EPI_WAVE_SYNC
-#define MDD_PIPE_EPI_WAVE_SYNC 1   // k_gemm_pipe: the waves of a block run their epilogues independently (wave-private staging)
-#endif
-#ifndef MDD_PIPE_FAST_GELU
-#define MDD_PIPE_FAST_GELU 1   // k_gemm_pipe: GELU, GELU', GELU'' from the 1.5e-7 erf approximation with one shared exponential
-#endif
-#ifndef MDD_PIPE_ACT1
-#define MDD_PIPE_ACT1 1      // 1: the GELU-epilogue launches (fc1 forward, fc2 data gradient: 3072-wide outputs, two to five
-                             // stashed tensors per output tile) run on k_gemm_pipe too.  Per-launch it looks slower -- with one block
-                             // per CU nothing overlaps those HBM-bound epilogues (312 vs 232 us per launch inside configs[4]) -- but the iteration is faster with it (426 vs 445 ms): 0 is kept for the record
-#endif
 #ifndef MDD_CONV_GEMM_RELU_TU   // (the ReLU translation unit has no pipelined-kernel launches: see launch_conv_gemm_)
 template <int N_> DEVI void wait_vm() {
   __builtin_amdgcn_s_waitcnt((N_ & 0xF) | ((N_ >> 4) << 14) | (0x7 << 4) | (0xF << 8));
@@ -636,9 +599,11 @@ DEVI void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
 template <int ACT_>
 __global__ __launch_bounds__(512, 1) void k_gemm_pipe(const KArgs p) {
   typedef bf16 AT;
-  constexpr int ACT = ACT_ == 1 ? (MDD_PIPE_FAST_GELU ? 2 : 1) : 0;
+  // GELU, GELU', GELU'' from the 1.5e-7 erf approximation with one shared exponential
+  constexpr int ACT = ACT_ == 1 ? 2 : 0;
   constexpr int TM = 4, TN = 2, MODE = 0, CE = 8, BM = 256;
-  constexpr bool IBK = false, EPI_WAVE_SYNC = MDD_PIPE_EPI_WAVE_SYNC != 0;
+  // the waves of a block run their epilogues independently (wave-private staging)
+  constexpr bool IBK = false, EPI_WAVE_SYNC = true;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ConvGeom& G = p.g;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 2, wn = wave & 3;
@@ -770,7 +735,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pipe(const KArgs p) {
   }
   if (wm == 0) raw_barrier();
   __syncthreads();
-#define MDD_EPI_HOISTED MDD_PIPE_EPI_HOIST
+#define MDD_EPI_HOISTED 1   // first group of stash loads of a 32-row block issued before its LDS transposition
 #include "conv_gemm_epilogue.inc"
 #undef MDD_EPI_HOISTED
 }
@@ -779,7 +744,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pipe(const KArgs p) {
 bool launch_pipe_gemm(const KArgs& a, hipStream_t st) {
   const ConvGeom& g = a.g;
   const bool pw = g.k == 1 && g.stride == 1 && g.pad == 0 && g.groups == 1;
-  if (!MDD_PIPE_ACT1 && a.ep.act == 1) return false;
   if (!pipe_kernels_enabled() || !pw || g.prec != 0 || g.kc < MDD_PIPE_MIN || g.nc < MDD_PIPE_MIN || (g.kc & 63) || (g.nc & 7) || (g.ca_tot & 7) ||
       (g.co_tot & 7) || a.M < 8192 || a.ep.ib != nullptr || (int64_t)a.M * g.ca_tot * 2 >= (1ll << 31) ||
       (int64_t)g.nc * g.kc * 2 >= (1ll << 31))
@@ -812,7 +776,7 @@ void launch_cfg(const KArgs& a, hipStream_t st) {
   k.mtiles = (a.M + BM - 1) / BM;
   if (MODE == 2) k.mtiles = 4 * ((a.g.nimg * (a.g.ho / 2) * (a.g.wo / 2) + BM - 1) / BM);
   k.ntiles = (a.g.nc + BN - 1) / BN;
-  size_t shm = (MDD_SINGLE_BUF ? 1 : 2) * (BM + BN) * 128;
+  size_t shm = (BM + BN) * 128;
   if (MODE == 4) shm = (size_t)(BM + 2 * a.g.wo + 3) * 128 + (size_t)3 * BN * 128;   // slab + zero row + B stage (3 taps)
   size_t shm_epi = 4 * (size_t)32 * (TN * 32 + 4) * sizeof(float);  // per-wave transpose, 32 rows at a time
   if (shm_epi > shm) shm = shm_epi;
@@ -903,13 +867,7 @@ void launch_conv_gemm_(const ConvGeom& g, const AT* A1, const AT* B1, const AT* 
 #endif
   if (g.nc <= 32) MDD_DISPATCH(4, 1, 1, 1);        // 128 x 32  (stem)
   else if (g.nc <= 64) MDD_DISPATCH(4, 1, 2, 2);   // 256 x 64  (group width 64)
-#if MDD_BIG_TILE == 0
   else MDD_DISPATCH(2, 2, 2, 2);                   // 128 x 128
-#elif MDD_BIG_TILE == 1
-  else MDD_DISPATCH(4, 1, 1, 2);                   // 128 x 64
-#else
-  else MDD_DISPATCH(2, 2, 1, 2);                   // 64 x 128
-#endif
 #undef MDD_DISPATCH
 #undef MDD_DISPATCH_P
 }

@@ -30,31 +30,17 @@
 
 #include "kernels.h"
 
-#ifndef MDD_WG_SINGLE_BUF
-#define MDD_WG_SINGLE_BUF 1
-#endif
-#ifndef MDD_WG_PF2
-#define MDD_WG_PF2 0
-#endif
 #ifndef MDD_WG_MIN_WAVES
 #define MDD_WG_MIN_WAVES 1
 #endif
 #ifndef MDD_WG_PIPE_MIN
 #define MDD_WG_PIPE_MIN 768  // narrowest layer (channels in and out) taken by the 256 x 256 pipelined kernel
 #endif
-#ifndef MDD_WG_SLAB
-#define MDD_WG_SLAB 1     // grouped 3x3 stride-1 convolutions with 64-channel groups on k_wgrad_slab (all nine taps per pass)
-#endif
 #ifndef MDD_WGP_ABL
 #define MDD_WGP_ABL 0   // timing experiments on k_wgrad_pipe (wrong results): 1 no MFMAs, 2 no LDS-DMA, 4 no fragment reads, 8 no write-out
 #endif
 #ifndef MDD_WG_TSTEP_SCALE
 #define MDD_WG_TSTEP_SCALE 1.0   // split policy of k_conv_wgrad: < 1 weighs a K-step less = fewer, longer blocks (less slab traffic, less CU time)
-#endif
-#ifndef MDD_WGP_GROUP_SPLITS
-#define MDD_WGP_GROUP_SPLITS 1   // pixel chunks of a grouped launch (0 = the cost model's choice): with ONE chunk the 108 tiles of a ViT layer go
-                                 // straight into the gradient -- no partial tiles, no combine launch, and 148 CUs stay with the other stream
-                                 // (measured: 1 chunk 407.0, 2 chunks (the model) 409.8, 3 chunks 418.4 ms per configs[4] iteration)
 #endif
 #ifndef MDD_WGP_SLOTS
 #define MDD_WGP_SLOTS 8    // half-tile slots of k_wgrad_pipe's LDS ring (16 KB each); half-tiles are issued SLOTS-2 phases ahead.  The K loop is
@@ -81,13 +67,12 @@ typedef unsigned __attribute__((ext_vector_type(4))) u32x4;   // first-class 16-
 template <int ROWB> DEVI int wswz(int row) { return ROWB == 128 ? ((row >> 1) & 3) : (row & 7); }
 
 // PW: pointwise (1x1, stride 1, no padding) instance -- no gather state, no per-step pixel decode
-// PF2: two tiles in flight in staging registers (loads issued two K-steps before their LDS store)
 // SPLIT (fp32 storage only): split-bf16 math -- each fp32 element is split into hi = bf16(x) and
 // lo = bf16(x - hi) between the global load and the LDS store, into two bf16 planes with the bf16 path's
 // layout; the contraction is hh + hl + lh on v_mfma_f32_16x16x32_bf16 (the ll term is below 2^-16 relative).
 // F16OPS (with SPLIT; ConvGeom::prec == 3): the fp32 operands are rounded to ONE fp16 each (11 significand bits)
 // and multiplied by v_mfma_f32_16x16x32_f16 -- the precision experiment of DESIGN.md section 5
-template <class AT, int BCO, int BKP, int BKM, bool PW, bool PF2, bool SPLIT, bool F16OPS = false>
+template <class AT, int BCO, int BKP, int BKM, bool PW, bool SPLIT, bool F16OPS = false>
 __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArgs p) {
   constexpr int CE = 16 / (int)sizeof(AT);
   constexpr bool BF = sizeof(AT) == 2;
@@ -103,10 +88,10 @@ __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArg
   constexpr int WKW = BKP / WKP;                         // k' width per wave
   static_assert(DSL >= 1 && XSL >= 1, "tile too small for 256 threads");
   static_assert(TR || (BCO == 64 && BKP == 128), "f32 path: 64x128 tile only");
-  constexpr int NBUF = MDD_WG_SINGLE_BUF ? 1 : 2;   // LDS stages (registers hold the tile in flight)
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * (DTILE + XTILE)];
+  // one LDS stage (registers hold the tile in flight)
+  __shared__ __attribute__((aligned(16))) char smem[DTILE + XTILE];
   char* Ds = smem;
-  char* Xs = smem + NBUF * DTILE;
+  char* Xs = smem + DTILE;
 
   const ConvGeom& G = p.g;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -185,18 +170,16 @@ __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArg
   };
   if constexpr (!pointwise) init_rows();
 
-  constexpr int NST = PF2 ? 2 : 1;
-  u32x4 rdS[NST][DSL], rxS[NST][XSL];
-  bool biasS[NST] = {};
+  u32x4 rdS[DSL], rxS[XSL];   // staging registers: the tile in flight
+  bool biasS = false;
   float bsum[CE];
 #pragma unroll
   for (int e = 0; e < CE; ++e) bsum[e] = 0.f;
   const bool do_bias = p.dbias != nullptr && kpt == 0;
   const bool hi_only = SPLIT && p.g.prec == 2;   // attribution experiment: bf16 operands from an fp32 stash
 
-  auto load_tile = [&](auto SI, int it) {
-    constexpr int si = decltype(SI)::value;
-    u32x4* rd = rdS[si]; u32x4* rx = rxS[si];
+  auto load_tile = [&](int it) {
+    u32x4 *rd = rdS, *rx = rxS;   // (written through pointers: that keeps the kernels' code as it was with two sets)
     const bool second = it >= niter1;
     if constexpr (!pointwise) { if (it == niter1) init_rows(); }
     const int itl = second ? it - niter1 : it;
@@ -227,14 +210,11 @@ __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArg
       }
       rx[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx_, (int)(ok ? vo : OOB), so, 0));
     }
-    biasS[si] = do_bias && !second;
+    biasS = do_bias && !second;
   };
-  auto store_tile = [&](auto SI, int buf) {
-    constexpr int si = decltype(SI)::value;
-    const u32x4* rd = rdS[si]; const u32x4* rx = rxS[si];
-    const bool bias_now = biasS[si];
-    char* d = Ds + buf * DTILE;
-    char* x = Xs + buf * XTILE;
+  auto store_tile = [&]() {
+    char* d = Ds;
+    char* x = Xs;
     auto split_store = [&](char* plane_hi, int plane_bytes, int row_bytes, int r, int unit, const u32x4& raw) {
       unsigned h[4], l[4];
 #pragma unroll
@@ -259,14 +239,14 @@ __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArg
     for (int i = 0; i < DSL; ++i) {
       int r = drow + DSTEP * i;
       if constexpr (SPLIT) {
-        split_store(d, BKM * TD, TD, r, dcol ^ (wswz<TD>(r) << 2), rd[i]);
+        split_store(d, BKM * TD, TD, r, dcol ^ (wswz<TD>(r) << 2), rdS[i]);
       } else {
         int c = BF ? (dcol ^ (wswz<DROWB>(r) << 1)) : dcol;
-        *(u32x4*)(d + r * DROWB + c * 16) = rd[i];
+        *(u32x4*)(d + r * DROWB + c * 16) = rdS[i];
       }
-      if (bias_now) {
+      if (biasS) {
         float f[CE];
-        Chunk<AT>::unpack(__builtin_bit_cast(uint4, rd[i]), f);
+        Chunk<AT>::unpack(__builtin_bit_cast(uint4, rdS[i]), f);
 #pragma unroll
         for (int e = 0; e < CE; ++e) bsum[e] += f[e];
       }
@@ -275,10 +255,10 @@ __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArg
     for (int i = 0; i < XSL; ++i) {
       int r = xrow + XSTEP * i;
       if constexpr (SPLIT) {
-        split_store(x, BKM * TX, TX, r, xcol ^ (wswz<TX>(r) << 2), rx[i]);
+        split_store(x, BKM * TX, TX, r, xcol ^ (wswz<TX>(r) << 2), rxS[i]);
       } else {
         int c = BF ? (xcol ^ (wswz<XROWB>(r) << 1)) : xcol;
-        *(u32x4*)(x + r * XROWB + c * 16) = rx[i];
+        *(u32x4*)(x + r * XROWB + c * 16) = rxS[i];
       }
     }
   };
@@ -299,22 +279,17 @@ __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArg
 #pragma unroll
       for (int r = 0; r < 4; ++r) accb[i][j][r] = 0.f;
 
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, PF2 ? 1 : 0>;
   if (niter > 0) {
-    load_tile(S0{}, 0);
-    if (PF2 && niter > 1) load_tile(S1{}, 1);
-    store_tile(S0{}, 0);
+    load_tile(0);
+    store_tile();
   }
   __syncthreads();
 
-  // one K-step: tile `it` is in LDS; the staging set SN holds tile it+1; (PF2) the free set SF takes it+2
-  auto step = [&](auto SF, auto SN, int it) {
-    const int buf = NBUF == 2 ? (it & 1) : 0;
-    if constexpr (PF2) { if (it + 2 < niter) load_tile(SF, it + 2); }
-    else { if (it + 1 < niter) load_tile(SN, it + 1); }
-    const char* d = Ds + buf * DTILE;
-    const char* x = Xs + buf * XTILE;
+  // one K-step: tile `it` is in LDS; the staging registers take tile it+1
+  auto step = [&](int it) {
+    if (it + 1 < niter) load_tile(it + 1);
+    const char* d = Ds;
+    const char* x = Xs;
     if constexpr (SPLIT) {
       const int gq = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
       typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -406,18 +381,11 @@ __global__ __launch_bounds__(256, MDD_WG_MIN_WAVES) void k_conv_wgrad(const WArg
           }
       }
     }
-    if (NBUF == 1) __syncthreads();      // everyone is done reading the tile before it is replaced
-    if (it + 1 < niter) store_tile(SN, NBUF == 2 ? (buf ^ 1) : 0);
+    __syncthreads();      // everyone is done reading the tile before it is replaced
+    if (it + 1 < niter) store_tile();
     __syncthreads();
   };
-  if constexpr (PF2) {
-    for (int it = 0; it < niter; it += 2) {
-      step(S0{}, S1{}, it);
-      if (it + 1 < niter) step(S1{}, S0{}, it + 1);
-    }
-  } else {
-    for (int it = 0; it < niter; ++it) step(S0{}, S0{}, it);
-  }
+  for (int it = 0; it < niter; ++it) step(it);
 
   if (MDD_DBG_BITS(p) & 2) return;   // dbg bit1: no write-out (timing only)
   // ---- write-out.  Accumulator maps (operands (x, dy): rows = k', columns = co):
@@ -1022,7 +990,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_slab(const WArgs p) {
 
 bool launch_slab(WArgs a, float* slab, int64_t slab_floats, hipEvent_t ev_mid, hipStream_t st) {
   const ConvGeom& g = a.g;
-  if (!MDD_WG_SLAB || g.k != 3 || g.stride != 1 || g.pad != 1 || g.kc != 64 || g.nc != 64 || g.ha != g.ho || g.wa != g.wo ||
+  if (g.k != 3 || g.stride != 1 || g.pad != 1 || g.kc != 64 || g.nc != 64 || g.ha != g.ho || g.wa != g.wo ||
       g.wo > 90 || g.wo < 3 || (g.ca_tot & 7) || (g.co_tot & 7) || (int64_t)a.M * std::max(g.ca_tot, g.co_tot) * 2 >= (1ll << 31))
     return false;
   const int nsrc = a.dy2 ? 2 : 1;
@@ -1134,7 +1102,9 @@ bool launch_pipe_group(const WItem* it, int n, int M, float* slab, int64_t slab_
     const double t = waves * (steps * 0.9 + 8.0) + out_mb * sp * comb_us_per_mb;
     if (t < best) { best = t; splits = sp; }
   }
-  if (MDD_WGP_GROUP_SPLITS > 0 && n > 1 && tiles * MDD_WGP_GROUP_SPLITS >= 64) splits = MDD_WGP_GROUP_SPLITS;   // small groups: the model
+  // groups of 64 tiles or more: ONE pixel chunk (the 108 tiles of a ViT layer go straight into the gradient -- no partial
+  // tiles, no combine launch, and 148 CUs stay with the other stream); small groups: the model
+  if (n > 1 && tiles >= 64) splits = 1;
   int mchunk = ((M + splits - 1) / splits + 63) / 64 * 64;
   splits = (M + mchunk - 1) / mchunk;
   G.n = n; G.M = M; G.mchunk = mchunk; G.tiles = tiles;
@@ -1225,23 +1195,22 @@ void launch_cfg(WArgs a, float* slab, int64_t slab_floats, hipEvent_t ev_mid, hi
     int64_t n4 = out_floats / 4;
     k_wgrad_reduce<<<(unsigned)((n4 + 15) / 16), 256, 0, st>>>(a.dW, slab, n4, out_floats / 4, splits);
   };
-  constexpr bool PF2 = MDD_WG_PF2 && sizeof(AT) == 2 && BCO == 128;   // 2 waves/SIMD either way there
   if constexpr (sizeof(AT) == 4) {
     if (g.prec == 3) {
-      if (pw) k_conv_wgrad<AT, BCO, BKP, BKM, true, false, true, true><<<grid, 256, 0, st>>>(a);
-      else k_conv_wgrad<AT, BCO, BKP, BKM, false, false, true, true><<<grid, 256, 0, st>>>(a);
+      if (pw) k_conv_wgrad<AT, BCO, BKP, BKM, true, true, true><<<grid, 256, 0, st>>>(a);
+      else k_conv_wgrad<AT, BCO, BKP, BKM, false, true, true><<<grid, 256, 0, st>>>(a);
       finish();
       return;
     }
     if (g.prec != 0) {
-      if (pw) k_conv_wgrad<AT, BCO, BKP, BKM, true, false, true><<<grid, 256, 0, st>>>(a);
-      else k_conv_wgrad<AT, BCO, BKP, BKM, false, false, true><<<grid, 256, 0, st>>>(a);
+      if (pw) k_conv_wgrad<AT, BCO, BKP, BKM, true, true><<<grid, 256, 0, st>>>(a);
+      else k_conv_wgrad<AT, BCO, BKP, BKM, false, true><<<grid, 256, 0, st>>>(a);
       finish();
       return;
     }
   }
-  if (pw) k_conv_wgrad<AT, BCO, BKP, BKM, true, PF2, false><<<grid, 256, 0, st>>>(a);
-  else k_conv_wgrad<AT, BCO, BKP, BKM, false, false, false><<<grid, 256, 0, st>>>(a);
+  if (pw) k_conv_wgrad<AT, BCO, BKP, BKM, true, false><<<grid, 256, 0, st>>>(a);
+  else k_conv_wgrad<AT, BCO, BKP, BKM, false, false><<<grid, 256, 0, st>>>(a);
   finish();
 }
 

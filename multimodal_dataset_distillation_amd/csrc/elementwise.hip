@@ -4,10 +4,6 @@
 // All tensors are [n, h*w, c] with c contiguous; every access is a 16-byte chunk per lane.
 #include "kernels.h"
 
-#ifndef MDD_EW_TILED
-#define MDD_EW_TILED 1   // per-image tiled SE apply / gradient kernels (0: the flat grid-stride versions)
-#endif
-
 namespace {
 
 template <class AT> DEVI void ld_chunk(const AT* p, int64_t chunk_idx, float* f) {
@@ -591,7 +587,7 @@ void launch_se_apply(const AT* c3, const AT* c3_t, const float* gate, const floa
                      const AT* sc, const AT* sc_t, AT* xo, AT* xo_t, AT* ao, AT* ao_t, float ga,
                      float beta, int n, int hw, int c, hipStream_t st) {
   int64_t total = (int64_t)n * hw * (c / Chunk<AT>::N);
-  if (MDD_EW_TILED && tiled_ok(c, Chunk<AT>::N)) {
+  if (tiled_ok(c, Chunk<AT>::N)) {
     int rpb;
     const dim3 grid = tiled_grid(n, hw, c, Chunk<AT>::N, &rpb);
     if (c3_t)
@@ -639,7 +635,7 @@ void launch_se_apply_bwd(AT* c3bar, AT* c3bar_t, const AT* xbar, const AT* xbar_
                          const float* gate, const float* gate_t, const float* pbar,
                          const float* pbar_t, float ga, int n, int hw, int c, hipStream_t st) {
   int64_t total = (int64_t)n * hw * (c / Chunk<AT>::N);
-  if (MDD_EW_TILED && tiled_ok(c, Chunk<AT>::N)) {
+  if (tiled_ok(c, Chunk<AT>::N)) {
     int rpb;
     const dim3 grid = tiled_grid(n, hw, c, Chunk<AT>::N, &rpb);
     if (xbar_t)
@@ -682,7 +678,7 @@ template <class AT, bool RELU>
 void final_pool_bwd_(AT* cfbar, AT* cfbar_t, const float* ybar, const float* ybar_t,
                      const AT* cf, const AT* cf_t, int n, int hw, int c, hipStream_t st) {
   int64_t total = (int64_t)n * hw * (c / Chunk<AT>::N);
-  if (MDD_EW_TILED && tiled_ok(c, Chunk<AT>::N)) {
+  if (tiled_ok(c, Chunk<AT>::N)) {
     int rpb;
     const dim3 grid = tiled_grid(n, hw, c, Chunk<AT>::N, &rpb);
     if (cf_t)

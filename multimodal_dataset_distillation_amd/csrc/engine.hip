@@ -37,31 +37,6 @@ int mdd_set_error_msg(int code, const char* msg) {
   g_err = msg;
   return code;
 }
-#ifndef MDD_SIDE_PRIORITY
-#define MDD_SIDE_PRIORITY 0   // bit 0: weight-gradient stream at least priority; bit 1: text stream (experiment builds)
-#endif
-#ifndef MDD_SE_SIDE
-#define MDD_SE_SIDE 2            // forward passes: squeeze-excite gate chain beside conv3 -- 0: no (main stream),
-#endif                           // 1: on the side stream, 2: on a stream of its own with high queue priority
-#ifndef MDD_SE_W13
-#define MDD_SE_W13 0             // experiment (r03_experiments.md: +1 % time, rejected): squeeze-excite chain through
-                                 // W13 = W1 W3_hat (se_prep) -- one product fewer on the dependent chain, 24-48 more
-                                 // small products per pass off it; 0: p, h, gate / pb, qb in sequence
-#endif
-#ifndef MDD_VIT_FUSED_ATTENTION
-#define MDD_VIT_FUSED_ATTENTION 1   // bf16 ViT: attention through csrc/attn.hip (0: bgemm + softmax kernels, scores in HBM)
-#endif
-#ifndef MDD_VIT_FUSE_GELU
-#define MDD_VIT_FUSE_GELU 1      // ViT MLP: exact GELU (and its chain rule) in the epilogues of fc1 / fc2's data gradient
-#endif
-#ifndef MDD_TF_SPLIT
-#define MDD_TF_SPLIT 0           // experiment (profiles/r03_experiments.md: +2.7 % time, rejected): tangent-forward pass,
-#endif                           // the second source of every contraction, conv(a, w_t), depends on the primal stash only --
-                                 // it runs ahead on the side stream (idle in forward passes) into the tangent buffer and
-                                 // the main chain's conv(a_t, w) adds it in its epilogue
-#ifndef MDD_GRAPH
-#define MDD_GRAPH 0      // 1: mdd_unrolled_match replays a captured hipGraph (experiment build)
-#endif
 #define CHECK_ARG(cond, msg) \
   do { if (!(cond)) return mdd_set_error_msg(2, "mdd: invalid argument: " msg); } while (0)
 #define POST_LAUNCH(what) HIP_CHECK_RET(hipGetLastError())
@@ -352,7 +327,8 @@ struct Eng : mdd_engine {
       const int D = vit.dim, gp = S / vit.patch;
       Tk = 1 + gp * gp; sld = (Tk + 7) & ~7;
       CHECK_ARG(D % vit.heads == 0 && Tk <= 512, "heads must divide dim; at most 512 tokens");
-      fused_attn = MDD_VIT_FUSED_ATTENTION && sizeof(AT) == 2 && attention_fused_supported(Tk, D / vit.heads);
+      // bf16: attention through csrc/attn.hip (scores never reach HBM)
+      fused_attn = sizeof(AT) == 2 && attention_fused_supported(Tk, D / vit.heads);
       auto add_lin = [&](const std::string& name, int cin, int cout, int tokens, bool conv_shape) {
         ConvL L; L.cin = cin; L.cout = cout; L.k = 1; L.stride = 1; L.groups = 1; L.pad = 0;
         L.hin = 1; L.hout = 1; L.cin_pad = cin; L.tokens = tokens;
@@ -665,13 +641,6 @@ struct Eng : mdd_engine {
       plan(&wslab[0], wslab_floats, nullptr, -2); plan(&wslab[1], wslab_floats, nullptr, -2);
     }
     plan(&ln_stats, (int64_t)N * 4, nullptr, -2);
-    // squeeze-excite shortcut operands, per block (se_prep): W13 = W1 W3_hat [rd, mid], b13 = W1 b3 + b1, tangents
-    se13.resize(blks.size());
-    for (size_t b = 0; b < blks.size() && nf.se; ++b) {
-      const int64_t rm = (int64_t)blks[b].se.rd * blks[b].mid;
-      plan(&se13[b].W, rm, nullptr, -2); plan(&se13[b].W_t, rm, nullptr, -2);
-      plan(&se13[b].b, blks[b].se.rd, nullptr, -2); plan(&se13[b].b_t, blks[b].se.rd, nullptr, -2);
-    }
     plan(&lossw, loss_work_floats(N, feat), nullptr, -2);
     sets.resize(nslots);
     for (int k = 0; k < nslots; ++k) plan_set(sets[k], k);
@@ -736,17 +705,9 @@ struct Eng : mdd_engine {
       const char* env = getenv("MDD_SIDE_STREAM");
       use_side = !(env && env[0] == '0');
 #endif
-#if MDD_SIDE_PRIORITY
-      // experiment: the weight-gradient (1) / text (2) streams below the caller's stream in queue priority
-      int prio_lo = 0, prio_hi = 0;
-      HIP_CHECK_RET(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));   // lo = least priority (largest number)
-      if (use_side) HIP_CHECK_RET(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, (MDD_SIDE_PRIORITY & 1) ? prio_lo : 0));
-      if (use_side) HIP_CHECK_RET(hipStreamCreateWithPriority(&tside, hipStreamNonBlocking, (MDD_SIDE_PRIORITY & 2) ? prio_lo : 0));
-#else
       if (use_side) HIP_CHECK_RET(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
       if (use_side) HIP_CHECK_RET(hipStreamCreateWithFlags(&tside, hipStreamNonBlocking));
-#endif
-      if (use_side && MDD_SE_SIDE == 2) {
+      if (use_side) {
         int prio_lo_ = 0, prio_hi_ = 0;
         HIP_CHECK_RET(hipDeviceGetStreamPriorityRange(&prio_lo_, &prio_hi_));   // hi = greatest priority (smallest number)
         HIP_CHECK_RET(hipStreamCreateWithPriority(&gstream, hipStreamNonBlocking, prio_hi_));
@@ -774,15 +735,10 @@ struct Eng : mdd_engine {
   hipStream_t side = nullptr;
   bool use_side = true;
   ~Eng() override {   // streams / events created at bind(); the workspace belongs to the caller
-#if MDD_GRAPH
-    if (gexec) (void)hipGraphExecDestroy(gexec);
-#endif
     if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
     if (tside) { (void)hipStreamSynchronize(tside); (void)hipStreamDestroy(tside); }
     if (gstream) { (void)hipStreamSynchronize(gstream); (void)hipStreamDestroy(gstream); }
     for (auto e : evs) (void)hipEventDestroy(e);
-    for (auto e : tf_ev) if (e) (void)hipEventDestroy(e);
-    if (se13_ev) (void)hipEventDestroy(se13_ev);
     for (auto& p : prof) { if (!p.shared_a) (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   }
   std::vector<hipEvent_t> evs;
@@ -918,72 +874,15 @@ struct Eng : mdd_engine {
       gemm(L, g, in, wf + L.off_p, nullptr, nullptr, e, st);
     } else {
       e.mode = EPI_FWD_T; e.bias_t = th_t + L.off_b; e.out_raw = C_t; e.out_act = A_t; e.c = C;
-      if (in_t && tf_split_active) {   // conv(a, w_t) is already in C_t (tf_side_prepass): add it in the epilogue
-        e.add1 = C_t;
-        gemm(L, g, in_t, wf + L.off_p, nullptr, nullptr, e, st);
-      }
-      else if (in_t) gemm(L, g, in_t, wf + L.off_p, in, wf_t + L.off_p, e, st);
+      if (in_t) gemm(L, g, in_t, wf + L.off_p, in, wf_t + L.off_p, e, st);
       else gemm(L, g, in, wf_t + L.off_p, nullptr, nullptr, e, st);
     }
   }
-  // Tangent-forward pass, second sources: raw conv(a, w_t) of every layer whose input carries a tangent, written into the
-  // layer's tangent buffer on the side stream.  They depend on the primal stash and the packed tangent weights only, so
-  // the whole sequence is enqueued at the start of the pass and runs beside the main chain; one event per block.
-  bool tf_split_active = false;
-  std::vector<hipEvent_t> tf_ev;     // [0] stem, [1 + b] block b, [nb + 1] final conv
-  void tf_raw(const ConvL& L, const AT* in, AT* dst, hipStream_t s2) {
-    ConvGeom g = gfwd(L);
-    ConvEpi e; memset(&e, 0, sizeof e);
-    e.mode = EPI_FWD; e.out_raw = dst; e.beta = 1.f;
-    gemm(L, g, in, wf_t + L.off_p, nullptr, nullptr, e, s2);
-  }
-  void tf_side_prepass(ActSet& P, ActSet& Q, hipStream_t st) {
-    const int nb = (int)blks.size();
-    if (tf_ev.size() < (size_t)nb + 2) {
-      tf_ev.resize(nb + 2, nullptr);
-      for (auto& e : tf_ev)
-        if (!e) ck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreateWithFlags");
-    }
-    fork(st);                         // after ws_forward: the packed tangent weights exist
-    hipStream_t s2 = side;
-    for (int i = 1; i < 4; ++i) tf_raw(convs[stem[i]], P.As[i - 1], i == 3 ? Q.X[0] : Q.Cs[i], s2);
-    ck(hipEventRecord(tf_ev[0], s2), "hipEventRecord");
-    for (int b = 0; b < nb; ++b) {
-      const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
-      if (B.ds >= 0) tf_raw(convs[B.ds], B.stride == 2 ? pa.P : P.A[b], qa.SC, s2);
-      tf_raw(convs[B.c1], P.A[b], qa.C1, s2);
-      tf_raw(convs[B.c2], pa.A1, qa.C2, s2);
-      tf_raw(convs[B.c2b], pa.A2, qa.C2b, s2);
-      tf_raw(convs[B.c3], pa.A2b, qa.C3, s2);
-      ck(hipEventRecord(tf_ev[1 + b], s2), "hipEventRecord");
-    }
-    tf_raw(convs[fin], P.X[nb], Q.CF, s2);
-    ck(hipEventRecord(tf_ev[nb + 1], s2), "hipEventRecord");
-  }
-  void tf_wait(int i, hipStream_t st) {
-    if (tf_split_active) ck(hipStreamWaitEvent(st, tf_ev[i], 0), "hipStreamWaitEvent");
-  }
-
   // Weight-gradient work is queued while a block's data-gradient chain is enqueued on the main
   // stream and released to the side stream with ONE event per block (flush_w): an event record is a
   // barrier packet on the main queue (~8-12 us bubble each), and nothing on the main stream waits for
   // these results before the end of the pass.
   static constexpr bool MAIN_TAIL = true;
-#ifndef MDD_VIT_FUSE_ADD_LN
-#define MDD_VIT_FUSE_ADD_LN 1    // ViT: a residual sum is formed by the LayerNorm kernel that reads it (mdd_op_add_layernorm)
-#endif
-#ifndef MDD_WGRAD_GROUP
-#define MDD_WGRAD_GROUP 1        // the wide pointwise layers queued between two flushes share one weight-gradient launch
-#endif
-#ifndef MDD_FLUSH_EVERY
-#define MDD_FLUSH_EVERY 1        // release queued weight gradients to the side stream every this many blocks
-#endif
-#ifndef MDD_TAIL_MAIN
-#define MDD_TAIL_MAIN 2          // how many of the stem's weight gradients run on the main stream at the pass's tail
-#endif
-#ifndef MDD_FWD_SHORTCUT_SIDE
-#define MDD_FWD_SHORTCUT_SIDE 1  // forward passes: shortcut branch (avg-pool + 1x1 conv) on the side stream
-#endif
   std::vector<std::function<void(hipStream_t)>> wq;
   // wide pointwise layers (the ViT linears) queued since the last flush: launched together, up to four per launch
   // (csrc/conv_wgrad.hip launch_conv_wgrad_group: a layer's 108 tiles need two pixel chunks instead of seven)
@@ -1025,7 +924,8 @@ struct Eng : mdd_engine {
   void conv_bwd_w(bool T, const ConvL& L, const AT* dy, const AT* dy_t, const AT* x, const AT* x_t,
                   float* dwf_, float* dwf_t_, float* gout, hipStream_t) {
     const ConvL* Lp = &L;
-    if (sizeof(AT) == 2 && MDD_WGRAD_GROUP && !prof_on && conv_wgrad_group_takes(gfwd(L))) {
+    // the wide pointwise layers queued between two flushes share one weight-gradient launch
+    if (sizeof(AT) == 2 && !prof_on && conv_wgrad_group_takes(gfwd(L))) {
       WgQ q; q.L = Lp; q.it.g = gfwd(L);
       if (!T) { q.it.dy1 = dy; q.it.x1 = x; q.it.dy2 = nullptr; q.it.x2 = nullptr; q.it.dW = dwf_ + L.off_p; }
       else { q.it.dy1 = dy_t; q.it.x1 = x; q.it.dy2 = x_t ? dy : nullptr; q.it.x2 = x_t; q.it.dW = dwf_t_ + L.off_p; }
@@ -1115,7 +1015,7 @@ struct Eng : mdd_engine {
     for (int l = 0; l < vit.depth; ++l) {
       const VitBlkL& B = vblk[l]; VitActs& pa = P.vb[l]; VitActs& qa = Q.vb[l];
       const AT *x = P.X[l], *x_t = T ? Q.X[l] : nullptr;
-      if (MDD_VIT_FUSE_ADD_LN && l > 0) {
+      if (l > 0) {
         // x_l = x2_{l-1} + fc2 output (still in TMP) is formed by the kernel that normalises it
         VitActs& pp = P.vb[l - 1]; VitActs& qp = Q.vb[l - 1];
         VIT_RC(mdd_op_add_layernorm(VDT, M, D, vit.eps, pp.X2, T ? qp.X2 : nullptr, P.TMP, T ? Q.TMP : nullptr, P.X[l],
@@ -1147,25 +1047,20 @@ struct Eng : mdd_engine {
         VIT_RC(mdd_op_bgemm(bdt(), 0, 0, &ad.o, pa.P, qa.P, v, v_t, nullptr, qa.O, st));
       }
       conv_fwd(T, convs[B.proj], pa.O, qa.O, P.TMP, Q.TMP, nullptr, nullptr, 1.f, th, th_t, st);
-      if (MDD_VIT_FUSE_ADD_LN) {
-        VIT_RC(mdd_op_add_layernorm(VDT, M, D, vit.eps, x, x_t, P.TMP, T ? Q.TMP : nullptr, pa.X2, T ? qa.X2 : nullptr,
-                                    th + B.ln2_w, tp(th_t + B.ln2_w), th + B.ln2_b, tp(th_t + B.ln2_b), pa.N2,
-                                    T ? qa.N2 : nullptr, st));
-      } else {
-        launch_add2<AT>(pa.X2, T ? qa.X2 : nullptr, x, x_t, P.TMP, T ? Q.TMP : nullptr, (int64_t)M * D, st);
-        VIT_RC(mdd_op_layernorm(VDT, M, D, vit.eps, pa.X2, T ? qa.X2 : nullptr, th + B.ln2_w, tp(th_t + B.ln2_w),
-                                th + B.ln2_b, tp(th_t + B.ln2_b), pa.N2, T ? qa.N2 : nullptr, st));
-      }
+      // a residual sum is formed by the LayerNorm kernel that reads it
+      VIT_RC(mdd_op_add_layernorm(VDT, M, D, vit.eps, x, x_t, P.TMP, T ? Q.TMP : nullptr, pa.X2, T ? qa.X2 : nullptr,
+                                  th + B.ln2_w, tp(th_t + B.ln2_w), th + B.ln2_b, tp(th_t + B.ln2_b), pa.N2,
+                                  T ? qa.N2 : nullptr, st));
       // fc1 with the exact GELU in its epilogue (C and A = gelu(C) written by the contraction; tangent: C_t and
       // A_t = gelu'(C) C_t) wherever the GELU instance of the kernel exists for this width
-      if (MDD_VIT_FUSE_GELU && conv_gemm_supports_gelu(gfwd(convs[B.fc1]))) {
+      if (conv_gemm_supports_gelu(gfwd(convs[B.fc1]))) {
         conv_fwd(T, convs[B.fc1], pa.N2, qa.N2, pa.C, qa.C, pa.A, qa.A, 1.f, th, th_t, st, 1);
       } else {
         conv_fwd(T, convs[B.fc1], pa.N2, qa.N2, pa.C, qa.C, nullptr, nullptr, 1.f, th, th_t, st);
         VIT_RC(mdd_op_gelu(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, pa.A, T ? qa.A : nullptr, st));
       }
       conv_fwd(T, convs[B.fc2], pa.A, qa.A, P.TMP, Q.TMP, nullptr, nullptr, 1.f, th, th_t, st);
-      if (!(MDD_VIT_FUSE_ADD_LN && l + 1 < vit.depth))    // otherwise formed by the next layer's first LayerNorm
+      if (l + 1 == vit.depth)    // otherwise formed by the next layer's first LayerNorm
         launch_add2<AT>(P.X[l + 1], T ? Q.X[l + 1] : nullptr, pa.X2, T ? qa.X2 : nullptr, P.TMP, T ? Q.TMP : nullptr,
                         (int64_t)M * D, st);
     }
@@ -1224,7 +1119,7 @@ struct Eng : mdd_engine {
       const AT *xb = O.XB[l + 1], *xb_t = Q.XB[l + 1];
       // MLP branch
       lin_bwd_w(T, convs[B.fc2], xb, xb_t, pa.A, qa.A, gout, st);
-      if (MDD_VIT_FUSE_GELU && conv_gemm_supports_gelu(gdgrad(convs[B.fc2]))) {
+      if (conv_gemm_supports_gelu(gdgrad(convs[B.fc2]))) {
         // fc2's data gradient with the GELU chain rule in its epilogue: raw AB (stashed: the tangent pass needs it)
         // and CB = gelu'(C) AB; tangent: CB_t = (gelu'(Dual(C, C_t)) Dual(AB, AB_t)).t from the stashed C, C_t, AB
         ConvEpi eg = epi_act(T, oa.AB, oa.CB, qa.CB, pa.C, qa.C, 1.f, nullptr, nullptr);
@@ -1335,7 +1230,7 @@ struct Eng : mdd_engine {
       if (B.ds >= 0) {
         // the shortcut (avg-pool + 1x1 conv) only meets the residual branch at the residual sum: side stream
         hipStream_t ss = st;
-        if (use_side && MDD_FWD_SHORTCUT_SIDE) { fork(st); ss = side; sc_forked = true; }
+        if (use_side) { fork(st); ss = side; sc_forked = true; }
         const AT *din = a, *din_t = a_t;
         if (B.stride == 2) {
           launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
@@ -1463,9 +1358,6 @@ struct Eng : mdd_engine {
     launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
                           wf_t, wt_t, st);
     if (!T) launch_img_gather_nhwc<AT>(P.X0, image, idx, N, 3, S, S, 8, st);
-    se_prep(T, th, th_t, st);
-    tf_split_active = T && use_side && MDD_TF_SPLIT;
-    if (tf_split_active) { tf_side_prepass(P, Q, st); tf_wait(0, st); }
     const AT* in = P.X0; const AT* in_t = nullptr;
     for (int i = 0; i < 4; ++i) {
       bool last = i == 3;
@@ -1480,13 +1372,11 @@ struct Eng : mdd_engine {
       const AT *x = P.X[b], *x_t = Q.X[b], *a = P.A[b], *a_t = Q.A[b];
       const AT *sc = x, *sc_t = x_t;
       bool sc_forked = false;
-      tf_wait(1 + b, st);
       if (B.ds >= 0) {
         // the shortcut (avg-pool + 1x1 conv) only meets the residual branch at the SE apply: it runs on
-        // the side stream, which is idle during forward passes (not in a split tangent pass: the side stream is busy
-        // with the second sources then)
+        // the side stream, which is idle during forward passes
         hipStream_t ss = st;
-        if (use_side && MDD_FWD_SHORTCUT_SIDE && !tf_split_active) { fork(st); ss = side; sc_forked = true; }
+        if (use_side) { fork(st); ss = side; sc_forked = true; }
         const AT *din = a, *din_t = a_t;
         if (B.stride == 2) {
           launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
@@ -1506,23 +1396,15 @@ struct Eng : mdd_engine {
       bool g_forked = false;
       {
         hipStream_t gs = st;
-        if (use_side && MDD_SE_SIDE == 1) { fork(st); gs = side; sc_forked = true; }
-        if (use_side && MDD_SE_SIDE == 2 && gstream) { fork_to(gstream, st); gs = gstream; g_forked = true; }
-        se_prep_wait(gs);
+        if (use_side && gstream) { fork_to(gstream, st); gs = gstream; g_forked = true; }
         launch_pool_mean<AT>(T ? qa.q : pa.q, T ? qa.A2b : pa.A2b, N, hw, B.mid, gs);
-        if (MDD_SE_W13) {
-          // h = relu(q W13^T + b13)  (= relu(W1 (W3_hat q + b3) + b1): one K = mid product instead of two)
-          launch_linear_fwd(pa.h, T ? qa.h : nullptr, pa.q, T ? qa.q : nullptr, se13[b].W, T ? se13[b].W_t : nullptr,
-                            se13[b].b, T ? se13[b].b_t : nullptr, N, B.mid, rd, 1, lin_main, gs);
-        } else {
-          const ConvL& L3 = convs[B.c3];
-          launch_linear_fwd_w<AT>(pa.p, T ? qa.p : nullptr, pa.q, T ? qa.q : nullptr, wf + L3.off_p,
-                                  T ? wf_t + L3.off_p : nullptr, th + L3.off_b, T ? th_t + L3.off_b : nullptr, N,
-                                  B.mid, c, 1.f, gs);
-          launch_linear_fwd(pa.h, T ? qa.h : nullptr, pa.p, T ? qa.p : nullptr, th + B.se.off_w1,
-                            T ? th_t + B.se.off_w1 : nullptr, th + B.se.off_b1,
-                            T ? th_t + B.se.off_b1 : nullptr, N, c, rd, 1, lin_main, gs);
-        }
+        const ConvL& L3 = convs[B.c3];
+        launch_linear_fwd_w<AT>(pa.p, T ? qa.p : nullptr, pa.q, T ? qa.q : nullptr, wf + L3.off_p,
+                                T ? wf_t + L3.off_p : nullptr, th + L3.off_b, T ? th_t + L3.off_b : nullptr, N,
+                                B.mid, c, 1.f, gs);
+        launch_linear_fwd(pa.h, T ? qa.h : nullptr, pa.p, T ? qa.p : nullptr, th + B.se.off_w1,
+                          T ? th_t + B.se.off_w1 : nullptr, th + B.se.off_b1,
+                          T ? th_t + B.se.off_b1 : nullptr, N, c, rd, 1, lin_main, gs);
         launch_linear_fwd(pa.gate, T ? qa.gate : nullptr, pa.h, T ? qa.h : nullptr, th + B.se.off_w2,
                           T ? th_t + B.se.off_w2 : nullptr, th + B.se.off_b2,
                           T ? th_t + B.se.off_b2 : nullptr, N, rd, c, 2, lin_main, gs);
@@ -1531,24 +1413,13 @@ struct Eng : mdd_engine {
       bool lastb = b == nb - 1;
       if (sc_forked) join(st);
       if (g_forked) join_from(gstream, st);
-      if (MDD_SE_W13) {
-        // p = q W3_hat^T + b3 (the pooled conv3 output itself) is only needed by the weight gradients of the backward
-        // passes: formed behind the gate (after the event the main stream waits for), off the dependent chain
-        hipStream_t ps = g_forked ? gstream : st;
-        const ConvL& L3 = convs[B.c3];
-        launch_linear_fwd_w<AT>(pa.p, T ? qa.p : nullptr, pa.q, T ? qa.q : nullptr, wf + L3.off_p,
-                                T ? wf_t + L3.off_p : nullptr, th + L3.off_b, T ? th_t + L3.off_b : nullptr, N,
-                                B.mid, c, 1.f, ps);
-      }
       launch_se_apply<AT>(pa.C3, T ? qa.C3 : nullptr, pa.gate, T ? qa.gate : nullptr, sc,
                           T ? sc_t : nullptr, P.X[b + 1], T ? Q.X[b + 1] : nullptr,
                           lastb ? nullptr : P.A[b + 1], (T && !lastb) ? Q.A[b + 1] : nullptr, ga,
                           lastb ? 1.f : blks[b + 1].beta, N, hw, c, st);
     }
-    tf_wait(nb + 1, st);
     conv_fwd(T, convs[fin], P.X[nb], Q.X[nb], P.CF, Q.CF, nullptr, nullptr, 1.f, th, th_t, st);
-    if (tf_split_active) { join(st); tf_split_active = false; }
-    if (use_side && gstream) join_from(gstream, st);     // the trailing p products of the gate stream
+    if (use_side && gstream) join_from(gstream, st);     // everything enqueued on the gate stream
     int hwf = xh[nb] * xh[nb];
     launch_final_pool<AT>(P.y, T ? feat_out : nullptr, P.CF, T ? Q.CF : nullptr, N, hwf, feat, st);
     if (!T && feat_out && feat_out != P.y)
@@ -1573,9 +1444,7 @@ struct Eng : mdd_engine {
     if (repack) {
       launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
                             wf_t, wt_t, st);
-      se_prep(T, th, th_t, st);
     }
-    se_prep_wait(st);
     float* dw = O.dwf; float* dw_t = Q.dwf;
     // (no zero-fill of dwf: every conv's two-phase weight gradient overwrites its whole packed slice)
     HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
@@ -1611,11 +1480,7 @@ struct Eng : mdd_engine {
         float *gw2 = gout + B.se.off_w2, *gb2 = gout + B.se.off_b2, *gw1 = gout + B.se.off_w1,
               *gb1 = gout + B.se.off_b1, *gw3 = (T ? dw_t : dw) + L3.off_p, *gb3 = gout + L3.off_b;
         const int n_ = N, mid_ = B.mid;
-        float *pBw = oa.pB, *pBw_t = T ? qa.pB : nullptr;
-        const float *W1 = th + B.se.off_w1, *W1_t = T ? th_t + B.se.off_w1 : nullptr;
         wq.push_back([=](hipStream_t ws_) {
-          // pb = hb W1 (gradient w.r.t. the pooled conv3 output): only the weight gradients need it
-          if (MDD_SE_W13) launch_linear_dgrad(pBw, pBw_t, hB, hB_t, W1, W1_t, nullptr, n_, c, rd, wlin(), ws_);
           launch_linear_wgrad(gw2, gb2, zB, zB_t, hh, hh_t, n_, rd, c, wlin(), ws_);
           launch_linear_wgrad(gw1, gb1, hB, hB_t, pp, pp_t, n_, c, rd, wlin(), ws_);
           // after conv3's own weight gradient (queued above: same stream, in order) has overwritten its slice
@@ -1625,16 +1490,10 @@ struct Eng : mdd_engine {
       launch_linear_dgrad(oa.hB, T ? qa.hB : nullptr, oa.zB, T ? qa.zB : nullptr,
                           th + B.se.off_w2, T ? th_t + B.se.off_w2 : nullptr, pa.h, N, rd, c,
                           lin_main, st);
-      if (MDD_SE_W13) {
-        // qb = hb W13 (= (hb W1) W3_hat): the gradient w.r.t. the mid-channel pooled vector in ONE K = rd product
-        launch_linear_dgrad(oa.qB, T ? qa.qB : nullptr, oa.hB, T ? qa.hB : nullptr, se13[b].W, T ? se13[b].W_t : nullptr,
-                            nullptr, N, B.mid, rd, lin_main, st);
-      } else {
-        launch_linear_dgrad(oa.pB, T ? qa.pB : nullptr, oa.hB, T ? qa.hB : nullptr, th + B.se.off_w1,
-                            T ? th_t + B.se.off_w1 : nullptr, nullptr, N, c, rd, lin_main, st);
-        launch_linear_fwd_w<AT>(oa.qB, T ? qa.qB : nullptr, oa.pB, T ? qa.pB : nullptr, wt + L3.off_p,
-                                T ? wt_t + L3.off_p : nullptr, nullptr, nullptr, N, c, B.mid, 1.f, st);
-      }
+      launch_linear_dgrad(oa.pB, T ? qa.pB : nullptr, oa.hB, T ? qa.hB : nullptr, th + B.se.off_w1,
+                          T ? th_t + B.se.off_w1 : nullptr, nullptr, N, c, rd, lin_main, st);
+      launch_linear_fwd_w<AT>(oa.qB, T ? qa.qB : nullptr, oa.pB, T ? qa.pB : nullptr, wt + L3.off_p,
+                              T ? wt_t + L3.off_p : nullptr, nullptr, nullptr, N, c, B.mid, 1.f, st);
       // residual branch
       {
         ConvEpi e3 = epi_act(T, oa.A2bB, oa.C2bB, qa.C2bB, pa.C2b, qa.C2b, 1.f, nullptr, nullptr);
@@ -1673,10 +1532,8 @@ struct Eng : mdd_engine {
     flush_w(st);   // stem: release each weight gradient at once (they are the tail of the pass)
     conv_bwd_d(T, convs[stem[3]], O.XB[0], Q.XB[0],
                epi_act(T, O.AsB[2], O.CsB[2], Q.CsB[2], P.Cs[2], Q.Cs[2], 1.f, nullptr, nullptr), st);
-    if (MDD_TAIL_MAIN < 3) {
-      conv_bwd_w(T, convs[stem[2]], O.CsB[2], Q.CsB[2], P.As[1], Q.As[1], dw, dw_t, gout, st);
-      flush_w(st);   // stem: release each weight gradient at once (they are the tail of the pass)
-    }
+    conv_bwd_w(T, convs[stem[2]], O.CsB[2], Q.CsB[2], P.As[1], Q.As[1], dw, dw_t, gout, st);
+    flush_w(st);   // stem: release each weight gradient at once (they are the tail of the pass)
     conv_bwd_d(T, convs[stem[2]], O.CsB[2], Q.CsB[2],
                epi_act(T, O.AsB[1], O.CsB[1], Q.CsB[1], P.Cs[1], Q.Cs[1], 1.f, nullptr, nullptr), st);
     conv_bwd_d(T, convs[stem[1]], O.CsB[1], Q.CsB[1],
@@ -1698,7 +1555,6 @@ struct Eng : mdd_engine {
     }
     // the last two weight gradients run on the main stream: at this point the side stream still has
     // the high-resolution layers' weight gradients queued and would otherwise be waited for
-    if (MDD_TAIL_MAIN >= 3) conv_bwd_w(T, convs[stem[2]], O.CsB[2], Q.CsB[2], P.As[1], Q.As[1], dw, dw_t, gout, st);
     conv_bwd_w(T, convs[stem[1]], O.CsB[1], Q.CsB[1], P.As[0], Q.As[0], dw, dw_t, gout, st);
     conv_bwd_w(T, convs[stem[0]], O.CsB[0], Q.CsB[0], P.X0, nullptr, dw, dw_t, gout, st);
     flush_w(st, MAIN_TAIL);
@@ -1734,41 +1590,6 @@ struct Eng : mdd_engine {
     return 0;
   }
   std::vector<const float*> slot_mask_ = std::vector<const float*>(65, nullptr);
-
-  // ---- squeeze-excite shortcut (round 3).  h_pre = W1 (W3_hat q + b3) + b1 = W13 q + b13 with W13 = W1 W3_hat
-  // [rd, mid]: the dependent chain of a block is pool -> (K = mid) -> (K = rd) instead of pool -> (K = mid) -> (K = C)
-  // -> (K = rd), and in the backward passes qb = hb W13 replaces pb = hb W1, qb = pb W3_hat on the critical path (pb
-  // and p are still formed, off that path, for the weight gradients).  W13 / b13 depend on theta only: they are built
-  // on the gate stream at the start of every pass that (re)packs the weights, beside the stem.
-  struct Se13 { float *W = nullptr, *W_t = nullptr, *b = nullptr, *b_t = nullptr; };
-  std::vector<Se13> se13;
-  hipEvent_t se13_ev = nullptr;
-  void se_prep(bool T, const float* th, const float* th_t, hipStream_t st) {
-    if (!MDD_SE_W13) return;
-    hipStream_t s2 = (use_side && gstream) ? gstream : st;
-    fork_to(s2, st);                   // after ws_forward: the packed (transposed) conv3 weights exist
-    for (size_t b = 0; b < blks.size(); ++b) {
-      const Blk& B = blks[b]; const ConvL& L3 = convs[B.c3];
-      const int C = B.se.c, rd = B.se.rd, mid = B.mid;
-      const float *W1 = th + B.se.off_w1, *b1 = th + B.se.off_b1, *b3 = th + L3.off_b;
-      // primal always (a tangent pass follows a repack at ITS theta_k); rows of W1 play the role of the batch
-      launch_linear_fwd_w<AT>(se13[b].W, nullptr, W1, nullptr, wt + L3.off_p, nullptr, nullptr, nullptr, rd, C, mid, 1.f, s2);
-      launch_matvec_bias(se13[b].b, nullptr, W1, nullptr, b3, nullptr, b1, nullptr, rd, C, s2);
-      if (T) {
-        const float *W1_t = th_t + B.se.off_w1, *b1_t = th_t + B.se.off_b1, *b3_t = th_t + L3.off_b;
-        launch_linear_fwd_w<AT>(se13[b].W, se13[b].W_t, W1, W1_t, wt + L3.off_p, wt_t + L3.off_p, nullptr, nullptr, rd, C,
-                                mid, 1.f, s2);
-        launch_matvec_bias(nullptr, se13[b].b_t, W1, W1_t, b3, b3_t, nullptr, b1_t, rd, C, s2);
-      }
-    }
-    if (s2 != st) {
-      if (!se13_ev) ck(hipEventCreateWithFlags(&se13_ev, hipEventDisableTiming), "hipEventCreateWithFlags");
-      ck(hipEventRecord(se13_ev, s2), "hipEventRecord");
-    }
-  }
-  void se_prep_wait(hipStream_t s) {   // a stream about to read W13 / b13
-    if (se13_ev && use_side && gstream && s != gstream) ck(hipStreamWaitEvent(s, se13_ev, 0), "hipStreamWaitEvent");
-  }
 
   int txt_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in,
                    const float* ybar_t_in, float* gout, float* dtext, const int64_t* idx,
@@ -1817,41 +1638,7 @@ struct Eng : mdd_engine {
   }
 
   // ------------------------------------------------------------------ whole outer iteration
-#if MDD_GRAPH
-  // Experiment (profiles/r02_experiments.md): the whole outer iteration captured into ONE hipGraph (three
-  // streams, their event edges included) and replayed while the call's arguments stay the same.
-  hipGraphExec_t gexec = nullptr;
-  std::vector<uint64_t> gkey;
   int unrolled_match(const mdd_iter_args* a, hipStream_t st) override {
-    if (!st || prof_on) return unrolled_match_enqueue(a, st);     // the legacy default stream cannot be captured
-    DevGuard guard(device_id);
-    std::vector<uint64_t> key;
-    const void* ptrs[] = {a->image_syn, a->text_syn, a->lr_img, a->lr_txt, a->theta0_img, a->theta0_txt,
-                          a->target_img, a->target_txt, a->perms, a->drop_masks, a->grad_image_syn,
-                          a->grad_text_syn, a->grad_lr, a->losses, (const void*)st};
-    for (const void* q : ptrs) key.push_back((uint64_t)(uintptr_t)q);
-    key.push_back((uint64_t)a->syn_steps); key.push_back((uint64_t)a->use_lr_as_scale);
-    uint32_t lsb; memcpy(&lsb, &a->logit_scale_const, 4); key.push_back(lsb);
-    if (!gexec || key != gkey) {
-      if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
-      HIP_CHECK_RET(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-      int rc = unrolled_match_enqueue(a, st);
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(st, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      HIP_CHECK_RET(e);
-      e = hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      HIP_CHECK_RET(e);
-      gkey = key;
-    }
-    HIP_CHECK_RET(hipGraphLaunch(gexec, st));
-    return 0;
-  }
-  int unrolled_match_enqueue(const mdd_iter_args* a, hipStream_t st) {
-#else
-  int unrolled_match(const mdd_iter_args* a, hipStream_t st) override {
-#endif
     CHECK_ARG(base, "workspace not bound");
     DevGuard guard(device_id);
     CHECK_ARG(a->syn_steps >= 1 && a->syn_steps <= K, "syn_steps exceeds the engine's slots");

@@ -15,10 +15,6 @@
 
 #define CHECK_ARG(cond, msg) \
   do { if (!(cond)) return mdd_set_error_msg(2, "mdd: invalid argument: " msg); } while (0)
-#ifndef MDD_VIT_MFMA_ATTENTION
-#define MDD_VIT_MFMA_ATTENTION 1   // bf16 storage: attention contractions on v_mfma_f32_32x32x16_bf16 (0: the S-generic FMA kernel)
-#endif
-
 #ifndef MDD_LN_BWD_ROWS
 #define MDD_LN_BWD_ROWS 16   // rows per block of k_ln_bwd (four waves, one row per wave at a time): the parameter-gradient sums cost
                              // one fp32 atomic per column and block
@@ -1102,9 +1098,9 @@ int mdd_op_bgemm(int dtype, int a_is_f32, int c_is_f32, const mdd_bgemm_desc* d,
   } else if (dtype == MDD_DTYPE_F32) {
     if (T) k_bgemm<Dual, float, float, float><<<grid, 256, 0, st>>>(p);
     else k_bgemm<float, float, float, float><<<grid, 256, 0, st>>>(p);
-  } else {
-    const bool done = MDD_VIT_MFMA_ATTENTION && (T ? bgemm_mfma<true>(p, a_is_f32, c_is_f32, grid, st)
-                                                     : bgemm_mfma<false>(p, a_is_f32, c_is_f32, grid, st));
+  } else {                                  // bf16 storage: matrix cores, the FMA kernel where they do not fit
+    const bool done = T ? bgemm_mfma<true>(p, a_is_f32, c_is_f32, grid, st)
+                        : bgemm_mfma<false>(p, a_is_f32, c_is_f32, grid, st);
     if (!done) {
       if (T) bgemm_types<Dual, bf16>(p, a_is_f32, c_is_f32, grid, st);
       else bgemm_types<float, bf16>(p, a_is_f32, c_is_f32, grid, st);

@@ -72,7 +72,7 @@ def main():
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--workload", default="c2")
     ap.add_argument("--stream", nargs="?", const="normal", default=None, choices=["normal", "high"],
-                    help="run on a non-default HIP stream (graph-capture builds); 'high' = a high-priority stream")
+                    help="run on a non-default HIP stream; 'high' = a high-priority stream")
     ap.add_argument("libs", nargs="*")
     a = ap.parse_args()
     if a.one:
