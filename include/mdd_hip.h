@@ -48,8 +48,8 @@ extern "C" {
 typedef struct mdd_engine mdd_engine;
 
 typedef struct mdd_config {
-  const char* variant; /* "nfnet_l0" | "nfnet_l1" | "nfnet_tiny" | "nf_resnet50" | "nf_resnet_tiny" | "vit_b16" |
-                          "vit_tiny16" | "vit_tiny16_cls" | "vit_micro" | "vit_micro_cls"                  */
+  const char* variant; /* "nfnet_l0" | "nfnet_l1" | "nfnet_tiny" | "nf_resnet50" | "nf_resnet_tiny" | "nf_regnet_b1" |
+                          "nf_regnet_tiny" | "vit_b16" | "vit_tiny16" | "vit_tiny16_cls" | "vit_micro" | "vit_micro_cls" */
   int32_t batch;       /* pairs per inner step (mini_batch_size, distill.py:511)          */
   int32_t num_queries; /* rows of image_syn / text_syn (distill.py:630)                    */
   int32_t image_size;  /* square input, multiple of 32                                     */
@@ -66,14 +66,19 @@ typedef struct mdd_config {
 
 const char* mdd_last_error(void);
 /* ABI version of this header: 2 = round 2 (mdd_config.keep_steps, MDD_DTYPE_BF16X2 / _F32_BF16OPS,
- * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2.  A binding built against another version
+ * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se.  A binding built against another version
  * must refuse to load. */
-#define MDD_ABI_VERSION 7
+#define MDD_ABI_VERSION 8
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
  * pipelined kernels; 0 routes them to the general kernels instead (process-wide; returns the previous setting).  For the
  * parity tests, which compare an iteration both ways, and for A/B timing. */
 int mdd_set_pipe_kernels(int enable);
+/* The bf16 grouped 3x3 convolutions with 8 channels per group (NF-RegNet's conv2): forward and data gradient run on a
+ * dedicated kernel (csrc/conv_g8.hip) for the geometries where it measured faster (1, the default); 0 routes them all to
+ * the general kernels, 2 routes every such geometry to the dedicated kernel (process-wide; returns the previous setting).
+ * For the parity tests, which run the same geometry both ways, and for A/B timing. */
+int mdd_set_group8_kernels(int enable);
 
 /* ---- engine lifetime and memory (the caller owns device memory: PyTorch caching allocator) */
 int mdd_engine_create(const mdd_config* cfg, mdd_engine** out);
@@ -220,6 +225,18 @@ int mdd_op_conv2d_wgrad2(int dtype, int nimg, int hin, int win, int cin, int cou
  *           each input element gathers the windows whose index points at it (no atomics) */
 int mdd_op_maxpool2d_3s2(int dtype, int mode, int n, int h, int w, int c, const void* x_dev, void* y_dev,
                          void* idx_dev, void* stream);
+
+/* Squeeze-excite in the MIDDLE of a block (NF-RegNet: on the mid channels between conv2 and conv3, followed by the
+ * activation): a3 = silu(ga * gate * c2), c2 / a3 NHWC [n, hw, c] in the storage type, gate [n, c] fp32.  c must be a
+ * multiple of 4 (MDD_DTYPE_F32) or 8 (MDD_DTYPE_BF16).  Tangent operands (`_t`) come all together or not at all; with
+ * them ONLY the `_t` outputs are written (the primal ones are inputs then: they hold the primal call's results).
+ *   mode 0  forward:  out = a3                                      (tangent: out_t)
+ *   mode 1  backward: out = c2bar = ga*gate*dsilu(u)*a3bar, u = ga*gate*c2 (+ qbar / hw per (image, channel) when qbar
+ *           [n, c] is given: the pooled path's share), zbar [n, c] = (ga * sum_hw c2*dsilu(u)*a3bar) * gate*(1-gate)
+ *           (tangent: out_t, zbar_t; qbar_t in the place of qbar) */
+int mdd_op_mid_se(int dtype, int mode, int n, int hw, int c, float ga, const void* c2, const void* c2_t, const float* gate,
+                  const float* gate_t, const void* a3bar, const void* a3bar_t, const float* qbar, void* out, void* out_t,
+                  float* zbar, float* zbar_t, void* stream);
 
 /* ---- synthetic-set evaluation: retrieval ranks.
  * Replaces the per-row host loops of reference epoch.py:140-156 (image->text: argsort of one similarity

@@ -15,7 +15,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmdd_hip.so")
 SOURCES = ["flat_ops.hip", "ws.hip", "elementwise.hip", "linear.hip", "head.hip", "conv_gemm.hip",
            "conv_gemm_relu.hip", "conv_wgrad.hip", "retrieval.hip", "collective.hip", "vit.hip", "attn.hip",
-           "nfres.hip", "engine.hip"]
+           "nfres.hip", "nfreg.hip", "conv_g8.hip", "engine.hip"]
 # sources that include another source file: rebuilt when it changes
 INCLUDES = {"conv_gemm_relu.hip": ["conv_gemm.hip"]}
 HEADERS = ["common.h", "kernels.h", "conv_gemm_epilogue.inc", os.path.join("..", "..", "include", "mdd_hip.h")]

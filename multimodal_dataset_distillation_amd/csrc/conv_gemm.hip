@@ -879,6 +879,9 @@ template <class AT>
 void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
                       const ConvEpi& ep, hipStream_t st) {
   if (ep.act == 3 && (ep.out_act || ep.mode == EPI_BWD_T)) { launch_conv_gemm_relu<AT>(g, A1, B1, A2, B2, ep, st); return; }
+  if constexpr (sizeof(AT) == 2) {   // grouped 3x3 with 8 channels per group: csrc/conv_g8.hip where it is routed there
+    if (g.k == 3 && g.kc == 8 && g.nc == 8 && launch_conv_g8(g, A1, B1, A2, B2, ep, st)) return;
+  }
   launch_conv_gemm_<AT, 0>(g, A1, B1, A2, B2, ep, st);
 }
 // GELU epilogues: pointwise contractions on the 128 x 128 tile (output width per group > 64)

@@ -58,10 +58,17 @@ struct NfCfg {
   float alpha, attn_gain, eps, gamma;
   // topology switches of the NormFreeNet family (NFNet: the defaults; NF-ResNet: 7x7 stem + max pool, ReLU, no
   // squeeze-excite, no conv2b, no final conv, classifier kept)
-  int stem_pool = 0;       // stem: 0 'deep_quad' (four 3x3 convs), 1 '7x7_pool' (7x7 / 2 conv, 3x3 / 2 max pool)
+  int stem_pool = 0;       // stem: 0 'deep_quad' (four 3x3 convs), 1 '7x7_pool' (7x7 / 2 conv, 3x3 / 2 max pool),
+                           // 2 '3x3' (one 3x3 / 2 conv)
   int relu = 0;            // activation: 0 SiLU, 1 ReLU (gamma above is the activation's)
   int se = 1, conv2b = 1, final_conv = 1;
   int classes = 0;         // > 0: classifier Linear(features, classes) after the global pool (features = its logits)
+  // NF-RegNet ('reg' block arithmetic): one-conv stem (stem_pool = 2, every stage strides), channel widths scaled by
+  // width_factor, bottleneck width from the block's INPUT channels (first_ratio in the very first block), squeeze-excite
+  // on the mid channels between conv2 and conv3 (module name `attn`), final conv of an absolute width
+  int reg = 0, se_mid = 0;
+  float width_factor = 1.f, first_ratio = 1.f;
+  int num_features = 0;    // > 0: final conv width make_divisible(width_factor * num_features, 8) instead of feat_mult
 };
 int make_divisible(double v, int divisor, double round_limit = 0.9) {
   int nv = std::max(divisor, (int)(v + divisor / 2.0) / divisor * divisor);
@@ -96,6 +103,20 @@ bool get_cfg(const char* variant, NfCfg& c) {
     c = res; int d[4] = {2, 1, 1, 1}; int ch[4] = {256, 128, 192, 256};
     memcpy(c.depths, d, sizeof d); memcpy(c.channels, ch, sizeof ch);
     c.stem_chs = 16; c.classes = 24; return true;
+  }
+  // timm 0.6.7 nfnet.py: nf_regnet_b1 = _nfreg_cfg(depths=(2, 4, 7, 7)): channels (48, 104, 208, 440), width_factor 0.75,
+  // stem '3x3' with channels[0] (scaled) channels, group_size 8, bottle_ratio 2.25, num_features 1280, reg=True,
+  // attn_layer 'se' with rd_ratio 0.5, act_layer 'silu'; the reference keeps the 1000-way head (networks.py:671-672)
+  NfCfg regc = {{2, 4, 7, 7}, {48, 104, 208, 440}, 48, 8, 2.25f, 1.0f, 0.5f,
+                0.2f, 2.0f, 1e-5f, 1.7881293296813965f};
+  regc.stem_pool = 2; regc.conv2b = 0; regc.classes = 1000;
+  regc.reg = 1; regc.se_mid = 1; regc.width_factor = 0.75f; regc.first_ratio = 1.0f; regc.num_features = 1280;
+  if (!strcmp(variant, "nf_regnet_b1")) { c = regc; return true; }
+  if (!strcmp(variant, "nf_regnet_tiny")) {  // build-defined miniature (tests): the ratio-1.0 first block, an identity-
+    // shortcut block, a stage-0 stride-2 downsample 40 -> 40, group counts 5, 11, 11, 23, 27, a final conv and a classifier
+    c = regc; int d[4] = {2, 1, 1, 1}; int ch[4] = {48, 104, 128, 160};
+    memcpy(c.depths, d, sizeof d); memcpy(c.channels, ch, sizeof ch);
+    c.num_features = 320; c.classes = 24; return true;
   }
   return false;
 }
@@ -213,6 +234,7 @@ struct Eng : mdd_engine {
   std::vector<ConvL> convs;
   std::vector<Blk> blks;
   int stem[4], fin;
+  int walker = 0;          // 0 NFNet (img_forward / img_backward), 1 NF-ResNet (res_*), 2 NF-RegNet (reg_*)
   int fpool = 0;           // width of the globally pooled features (= feat unless a classifier follows: NF-ResNet)
   int ract = 0;            // ConvEpi::act of the residual branches' fused epilogues (0 SiLU, 3 ReLU)
   ConvL stem_col;          // NF-ResNet: the 7x7 stem as a pointwise contraction over its columns (same packed weights)
@@ -372,11 +394,19 @@ struct Eng : mdd_engine {
     // the two walkers: NFNet (deep_quad stem, squeeze-excite, conv2b, final conv) and the plain residual one of
     // NF-ResNet (7x7_pool stem, none of those three); other mixes of the switches have no walker
     const bool nfnet_like = !nf.stem_pool && nf.se && nf.conv2b && nf.final_conv && !nf.classes;
-    const bool plain_res = nf.stem_pool && !nf.se && !nf.conv2b && !nf.final_conv;
-    CHECK_ARG(nfnet_like || plain_res, "internal: unsupported NormFreeNet topology");
+    const bool plain_res = nf.stem_pool == 1 && !nf.se && !nf.conv2b && !nf.final_conv;
+    const bool reg_like = nf.stem_pool == 2 && nf.reg && nf.se && nf.se_mid && !nf.conv2b && nf.final_conv && nf.classes &&
+                          !nf.relu;
+    CHECK_ARG(nfnet_like || plain_res || reg_like, "internal: unsupported NormFreeNet topology");
+    walker = plain_res ? 1 : (reg_like ? 2 : 0);
     ract = nf.relu ? 3 : 0;
     int prev = 3, h = S;
-    if (nf.stem_pool) {
+    if (nf.stem_pool == 2) {
+      // stem '3x3': one conv 3x3 / 2, no activation (its output is the raw stream)
+      stem[0] = add_conv("model.stem.conv", 3, make_divisible(nf.stem_chs * nf.width_factor, 8), 3, 2, 1, h);
+      stem[1] = stem[2] = stem[3] = -1;
+      h = convs[stem[0]].hout; prev = convs[stem[0]].cout;
+    } else if (nf.stem_pool) {
       // stem '7x7_pool': conv 7x7 / 2 (no activation), MaxPool2d(3, 2, padding=1)
       stem[0] = add_conv("model.stem.conv", 3, nf.stem_chs, 7, 2, 1, h);
       stem[1] = stem[2] = stem[3] = -1;
@@ -398,9 +428,10 @@ struct Eng : mdd_engine {
     for (int si = 0; si < 4; ++si) {
       for (int bi = 0; bi < nf.depths[si]; ++bi) {
         Blk B; std::string pre = "model.stages." + std::to_string(si) + "." + std::to_string(bi);
-        int stride = (bi == 0 && si > 0) ? 2 : 1;
-        int out = make_divisible(nf.channels[si], 8);
+        int stride = (bi == 0 && (si > 0 || nf.stem_pool == 2)) ? 2 : 1;
+        int out = make_divisible(nf.channels[si] * (double)nf.width_factor, 8);
         int mid = make_divisible(out * nf.bottle_ratio, 8);
+        if (nf.reg) mid = make_divisible(prev * (double)((si == 0 && bi == 0) ? nf.first_ratio : nf.bottle_ratio), 8);
         int groups = nf.group_size ? mid / nf.group_size : 1;
         if (nf.group_size && nf.group_size % 8 == 0) mid = nf.group_size * groups;
         B.stride = stride; B.cin = prev; B.cout = out; B.mid = mid; B.hin = h;
@@ -411,10 +442,17 @@ struct Eng : mdd_engine {
         B.c1 = add_conv(pre + ".conv1", prev, mid, 1, 1, 1, h);
         B.c2 = add_conv(pre + ".conv2", mid, mid, 3, stride, groups, h);
         B.c2b = nf.conv2b ? add_conv(pre + ".conv2b", mid, mid, 3, 1, groups, hout) : -1;
+        B.se.c = out; B.se.rd = 0; B.se.off_w1 = B.se.off_b1 = B.se.off_w2 = B.se.off_b2 = -1;
+        if (nf.se && nf.se_mid) {   // timm registers `attn` (on the mid channels) in front of conv3
+          B.se.c = mid; B.se.rd = make_divisible(mid * nf.se_rd_ratio, 8, 0.0);
+          B.se.off_w1 = add_param(pimg, pre + ".attn.fc1.weight", {B.se.rd, mid, 1, 1});
+          B.se.off_b1 = add_param(pimg, pre + ".attn.fc1.bias", {B.se.rd});
+          B.se.off_w2 = add_param(pimg, pre + ".attn.fc2.weight", {mid, B.se.rd, 1, 1});
+          B.se.off_b2 = add_param(pimg, pre + ".attn.fc2.bias", {mid});
+        }
         B.c3 = add_conv(pre + ".conv3", mid, out, 1, 1, 1, hout);
         CHECK_ARG(convs[B.c2].hout == hout, "internal: spatial plan");
-        B.se.c = out; B.se.rd = 0; B.se.off_w1 = B.se.off_b1 = B.se.off_w2 = B.se.off_b2 = -1;
-        if (nf.se) {
+        if (nf.se && !nf.se_mid) {
         B.se.rd = make_divisible(out * nf.se_rd_ratio, 8, 0.0);
         B.se.off_w1 = add_param(pimg, pre + ".attn_last.fc1.weight", {B.se.rd, out, 1, 1});
         B.se.off_b1 = add_param(pimg, pre + ".attn_last.fc1.bias", {B.se.rd});
@@ -430,7 +468,8 @@ struct Eng : mdd_engine {
       }
     }
     if (nf.final_conv) {
-    feat = (int)(nf.channels[3] * nf.feat_mult);
+    feat = nf.num_features > 0 ? make_divisible(nf.width_factor * (double)nf.num_features, 8)
+                               : (int)(nf.channels[3] * nf.feat_mult);
     fin = add_conv("model.final_conv", prev, feat, 1, 1, 1, h);
     } else {
       feat = prev; fin = -1;
@@ -562,9 +601,54 @@ struct Eng : mdd_engine {
     plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
     plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
   }
+  // NF-RegNet (one-conv stem, squeeze-excite between conv2 and conv3, final conv + classifier): the stem conv's raw
+  // output IS the stream X[0]; per block {C1, A1, C2, A2 = silu(ga*gate*C2), C3}, the gate chain {q, h, gate} and their
+  // gradients; the final conv's output and the pooled features in front of the classifier
+  void plan_set_reg(ActSet& s, int slot) {
+    const int nb = (int)blks.size();
+    const int64_t n = N;
+    s.X0 = nullptr;
+    if (slot >= 0) plan(&s.X0, n * S * S * 8, "IN", slot);   // the image has no tangent
+    plan(&s.X0B, n * S * S * 8, "INB", slot);
+    s.X.resize(nb + 1); s.A.resize(nb + 1); s.XB.resize(nb + 1); s.blk.resize(nb);
+    for (int b = 0; b <= nb; ++b) {
+      int64_t e = n * xh[b] * xh[b] * xc[b];
+      plan(&s.X[b], e, ("X" + std::to_string(b)).c_str(), slot);
+      plan(&s.XB[b], e, ("XB" + std::to_string(b)).c_str(), slot);
+      if (b < nb) plan(&s.A[b], e, ("A" + std::to_string(b)).c_str(), slot); else s.A[b] = nullptr;
+    }
+    for (int b = 0; b < nb; ++b) {
+      const Blk& B = blks[b]; BlockActs& a = s.blk[b];
+      memset(&a, 0, sizeof a);
+      std::string p = "b" + std::to_string(b) + ".";
+      int64_t ein = n * B.hin * B.hin, eout = n * B.hout * B.hout;
+      if (B.ds >= 0 && B.stride == 2) plan(&a.P, eout * B.cin, (p + "P").c_str(), slot);
+      if (B.ds >= 0) plan(&a.SC, eout * B.cout, (p + "SC").c_str(), slot);
+      plan(&a.C1, ein * B.mid, (p + "C1").c_str(), slot);   plan(&a.A1, ein * B.mid, (p + "A1").c_str(), slot);
+      plan(&a.C2, eout * B.mid, (p + "C2").c_str(), slot);  plan(&a.A2, eout * B.mid, (p + "A2").c_str(), slot);
+      plan(&a.C3, eout * B.cout, (p + "C3").c_str(), slot);
+      plan(&a.q, n * B.mid, (p + "q").c_str(), slot);       plan(&a.qB, n * B.mid, (p + "qB").c_str(), slot);
+      plan(&a.h, n * B.se.rd, (p + "h").c_str(), slot);     plan(&a.hB, n * B.se.rd, (p + "hB").c_str(), slot);
+      plan(&a.gate, n * B.mid, (p + "gate").c_str(), slot); plan(&a.zB, n * B.mid, (p + "zB").c_str(), slot);
+      plan(&a.C3B, eout * B.cout, (p + "C3B").c_str(), slot);
+      plan(&a.A2B, eout * B.mid, (p + "A2B").c_str(), slot);   plan(&a.C2B, eout * B.mid, (p + "C2B").c_str(), slot);
+      plan(&a.A1B, ein * B.mid, (p + "A1B").c_str(), slot);    plan(&a.C1B, ein * B.mid, (p + "C1B").c_str(), slot);
+      plan(&a.AinB, ein * B.cin, (p + "AinB").c_str(), slot);
+    }
+    int64_t ef = n * xh[nb] * xh[nb] * fpool;
+    plan(&s.CF, ef, "CF", slot); plan(&s.CFB, ef, "CFB", slot);
+    plan(&s.hin, n * fpool, "pooled", slot); plan(&s.hinB, n * fpool, "pooledB", slot);
+    plan(&s.y, n * feat, "y", slot); plan(&s.yB, n * feat, "yB", slot);
+    plan(&s.dwf, packed_total, "dwf", slot);
+    plan(&s.tx, n * Dt, "tx", slot); plan(&s.tp, n * feat, "tp", slot); plan(&s.tg, n * feat, "tg", slot);
+    plan(&s.tf, n * feat, "tf", slot); plan(&s.tr, n * feat, "tr", slot); plan(&s.ty, n * feat, "ty", slot);
+    plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
+    plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
+  }
   void plan_set(ActSet& s, int slot) {
     if (is_vit) { plan_set_vit(s, slot); return; }
-    if (nf.stem_pool) { plan_set_res(s, slot); return; }
+    if (walker == 1) { plan_set_res(s, slot); return; }
+    if (walker == 2) { plan_set_reg(s, slot); return; }
     int nb = (int)blks.size();
     auto nm = [&](const std::string& n) { return n; };
     int64_t n = N;
@@ -1344,6 +1428,159 @@ struct Eng : mdd_engine {
     return 0;
   }
 
+  // ================================================================== NF-RegNet image encoder (timm nf_regnet_b1)
+  // stem conv 3x3 / 2 -> blocks {a = beta*silu(x); shortcut = x or downsample(a); c2 = conv2(silu(conv1(a)));
+  // a3 = silu(attn_gain * gate(c2) * c2); x' = alpha*conv3(a3) + shortcut} -> final conv -> silu -> global average
+  // pool -> classifier.  Every stage strides; conv2 is grouped with 8 channels per group.  The gate chain (pool, two
+  // small-batch linears) sits on the critical path here: conv3 needs a3.
+  int reg_forward(bool T, int slot, const float* th, const float* th_t, const float* image, const int64_t* idx,
+                  float* feat_out, hipStream_t st) {
+    ActSet& P = sets[slot]; ActSet& Q = tn;
+    const int nb = (int)blks.size();
+    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
+    launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
+                          wf_t, wt_t, st);
+    if (!T) launch_img_gather_nhwc<AT>(P.X0, image, idx, N, 3, S, S, 8, st);
+    conv_fwd(T, convs[stem[0]], P.X0, nullptr, P.X[0], Q.X[0], P.A[0], Q.A[0], blks[0].beta, th, th_t, st);
+    for (int b = 0; b < nb; ++b) {
+      const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
+      const AT *a = P.A[b], *a_t = Q.A[b];
+      const AT *sc = P.X[b], *sc_t = Q.X[b];
+      bool sc_forked = false;
+      if (B.ds >= 0) {
+        // the shortcut (avg-pool + 1x1 conv) only meets the residual branch at the residual sum: side stream
+        hipStream_t ss = st;
+        if (use_side) { fork(st); ss = side; sc_forked = true; }
+        const AT *din = a, *din_t = a_t;
+        if (B.stride == 2) {
+          launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
+          din = pa.P; din_t = qa.P;
+        }
+        conv_fwd(T, convs[B.ds], din, din_t, pa.SC, qa.SC, nullptr, nullptr, 1.f, th, th_t, ss);
+        sc = pa.SC; sc_t = qa.SC;
+      }
+      const int hw = B.hout * B.hout, c = B.mid, rd = B.se.rd;
+      conv_fwd(T, convs[B.c1], a, a_t, pa.C1, qa.C1, pa.A1, qa.A1, 1.f, th, th_t, st);
+      conv_fwd(T, convs[B.c2], pa.A1, qa.A1, pa.C2, qa.C2, nullptr, nullptr, 1.f, th, th_t, st);
+      launch_pool_mean<AT>(T ? qa.q : pa.q, T ? qa.C2 : pa.C2, N, hw, c, st);
+      launch_linear_fwd(pa.h, T ? qa.h : nullptr, pa.q, T ? qa.q : nullptr, th + B.se.off_w1, tp(th_t + B.se.off_w1),
+                        th + B.se.off_b1, tp(th_t + B.se.off_b1), N, c, rd, 1, lin_main, st);
+      launch_linear_fwd(pa.gate, T ? qa.gate : nullptr, pa.h, T ? qa.h : nullptr, th + B.se.off_w2,
+                        tp(th_t + B.se.off_w2), th + B.se.off_b2, tp(th_t + B.se.off_b2), N, rd, c, 2, lin_main, st);
+      launch_mid_se_apply<AT>(pa.A2, T ? qa.A2 : nullptr, pa.C2, T ? qa.C2 : nullptr, pa.gate, T ? qa.gate : nullptr,
+                              nf.attn_gain, N, hw, c, st);
+      conv_fwd(T, convs[B.c3], pa.A2, qa.A2, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
+      if (sc_forked) join(st);
+      const bool lastb = b == nb - 1;
+      launch_resid_silu<AT>(pa.C3, T ? qa.C3 : nullptr, sc, T ? sc_t : nullptr, P.X[b + 1], T ? Q.X[b + 1] : nullptr,
+                            lastb ? nullptr : P.A[b + 1], (T && !lastb) ? Q.A[b + 1] : nullptr, nf.alpha,
+                            lastb ? 1.f : blks[b + 1].beta, (int64_t)N * hw * B.cout, st);
+    }
+    // final conv on the raw stream, final_act (SiLU) + global average pool, then the classifier (small-batch fp32 linear)
+    conv_fwd(T, convs[fin], P.X[nb], Q.X[nb], P.CF, Q.CF, nullptr, nullptr, 1.f, th, th_t, st);
+    const int hwf = xh[nb] * xh[nb];
+    launch_final_pool<AT>(P.hin, T ? Q.hin : nullptr, P.CF, T ? Q.CF : nullptr, N, hwf, fpool, st);
+    launch_linear_fwd(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_hw, tp(th_t + off_hw),
+                      th + off_hb, tp(th_t + off_hb), N, fpool, nf.classes, 0, lin_main, st);
+    if (!T && feat_out && feat_out != P.y)
+      HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    POST_WALK("reg_forward");
+    return 0;
+  }
+  int reg_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in, const float* ybar_t_in,
+                   float* gout, float* dimage, const int64_t* idx, const float* coef, float mul, bool repack, bool stash,
+                   hipStream_t st) {
+    ActSet& P = sets[slot]; ActSet& Q = tn;
+    ActSet& O = (!T && !stash) ? tn : P;  // where primal backward signals are written
+    const int nb = (int)blks.size();
+    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
+    if (repack)
+      launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
+                            wf_t, wt_t, st);
+    float* dw = O.dwf; float* dw_t = Q.dwf;
+    HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
+    if (!T && ybar_in != O.yB)
+      HIP_CHECK_RET(hipMemcpyAsync(O.yB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    const int hwf = xh[nb] * xh[nb];
+    launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N,
+                        fpool, nf.classes, lin_main, st);
+    launch_linear_dgrad(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_hw, tp(th_t + off_hw),
+                        nullptr, N, fpool, nf.classes, lin_main, st);
+    launch_final_pool_bwd<AT>(O.CFB, T ? Q.CFB : nullptr, O.hinB, T ? Q.hinB : nullptr, P.CF, T ? Q.CF : nullptr, N, hwf,
+                              fpool, st);
+    conv_bwd_w(T, convs[fin], O.CFB, Q.CFB, P.X[nb], Q.X[nb], dw, dw_t, gout, st);
+    conv_bwd_d(T, convs[fin], O.CFB, Q.CFB, epi_lin(T ? Q.XB[nb] : O.XB[nb], nullptr), st);
+    for (int b = nb - 1; b >= 0; --b) {
+      const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
+      BlockActs& oa = O.blk[b];
+      const AT *xb = O.XB[b + 1], *xb_t = Q.XB[b + 1];
+      const int hw = B.hout * B.hout, c = B.mid, rd = B.se.rd;
+      const int64_t eout = (int64_t)N * hw;
+      // x' = alpha*c3 + shortcut: conv3's output gradient is alpha times the block output's
+      launch_scale_act<AT>(T ? qa.C3B : oa.C3B, T ? xb_t : xb, nf.alpha, eout * B.cout, st);
+      conv_bwd_w(T, convs[B.c3], oa.C3B, qa.C3B, pa.A2, qa.A2, dw, dw_t, gout, st);
+      flush_w(st);
+      // a3bar (raw: the squeeze-excite backward applies the activation's chain rule)
+      conv_bwd_d(T, convs[B.c3], oa.C3B, qa.C3B, epi_lin(T ? qa.A2B : oa.A2B, nullptr), st);
+      // squeeze-excite backward: direct share of c2bar and the gate gradient in one pass, the gate's two linears, then
+      // the pooled path's share qbar / hw
+      launch_mid_se_bwd<AT>(oa.zB, T ? qa.zB : nullptr, oa.C2B, T ? qa.C2B : nullptr, pa.C2, T ? qa.C2 : nullptr, oa.A2B,
+                            T ? qa.A2B : nullptr, pa.gate, T ? qa.gate : nullptr, nf.attn_gain, N, hw, c, st);
+      launch_linear_dgrad(oa.hB, T ? qa.hB : nullptr, oa.zB, T ? qa.zB : nullptr, th + B.se.off_w2,
+                          tp(th_t + B.se.off_w2), pa.h, N, rd, c, lin_main, st);
+      launch_linear_dgrad(oa.qB, T ? qa.qB : nullptr, oa.hB, T ? qa.hB : nullptr, th + B.se.off_w1,
+                          tp(th_t + B.se.off_w1), nullptr, N, c, rd, lin_main, st);
+      launch_add_pooled<AT>(T ? qa.C2B : oa.C2B, T ? qa.qB : oa.qB, 1.f / (float)hw, N, hw, c, st);
+      {
+        const float *zB = oa.zB, *zB_t = T ? qa.zB : nullptr, *hh = pa.h, *hh_t = T ? qa.h : nullptr;
+        const float *hB = oa.hB, *hB_t = T ? qa.hB : nullptr, *qq = pa.q, *qq_t = T ? qa.q : nullptr;
+        float *gw2 = gout + B.se.off_w2, *gb2 = gout + B.se.off_b2, *gw1 = gout + B.se.off_w1, *gb1 = gout + B.se.off_b1;
+        const int n_ = N;
+        wq.push_back([=](hipStream_t ws_) {
+          launch_linear_wgrad(gw2, gb2, zB, zB_t, hh, hh_t, n_, rd, c, wlin(), ws_);
+          launch_linear_wgrad(gw1, gb1, hB, hB_t, qq, qq_t, n_, c, rd, wlin(), ws_);
+        });
+      }
+      conv_bwd_w(T, convs[B.c2], oa.C2B, qa.C2B, pa.A1, qa.A1, dw, dw_t, gout, st);
+      conv_bwd_d(T, convs[B.c2], oa.C2B, qa.C2B,
+                 epi_act(T, oa.A1B, oa.C1B, qa.C1B, pa.C1, qa.C1, 1.f, nullptr, nullptr), st);
+      conv_bwd_w(T, convs[B.c1], oa.C1B, qa.C1B, P.A[b], Q.A[b], dw, dw_t, gout, st);
+      // shortcut branch
+      const AT* add1 = nullptr;
+      if (B.ds >= 0) {
+        const AT* dsin = B.stride == 2 ? pa.P : P.A[b];
+        const AT* dsin_t = B.stride == 2 ? qa.P : Q.A[b];
+        conv_bwd_w(T, convs[B.ds], xb, xb_t, dsin, dsin_t, dw, dw_t, gout, st);
+        conv_bwd_d(T, convs[B.ds], xb, xb_t, epi_lin(dsS, nullptr), st);
+        if (B.stride == 2) {
+          launch_avgpool2_bwd<AT>(dsF, dsS, N, B.hin, B.hin, B.cin, 2, st);
+          add1 = dsF;
+        } else {
+          add1 = dsS;
+        }
+      }
+      // conv1 dgrad + pre-activation chain rule + identity shortcut:  XB[b] = beta*silu'(X[b])*Abar (+ XB[b+1])
+      conv_bwd_d(T, convs[B.c1], oa.C1B, qa.C1B,
+                 epi_act(T, oa.AinB, O.XB[b], Q.XB[b], P.X[b], Q.X[b], B.beta, add1,
+                         B.ds >= 0 ? nullptr : (T ? xb_t : xb)), st);
+      if (b == 0) flush_w(st);
+    }
+    // stem: the conv's raw output is the stream X[0], its gradient XB[0]
+    const ConvL& L0 = convs[stem[0]];
+    if (dimage) {
+      AT* x0b = T ? Q.X0B : O.X0B;
+      conv_bwd_d(T, L0, O.XB[0], Q.XB[0], epi_lin(x0b, nullptr), st);
+      launch_img_scatter_grad<AT>(dimage, x0b, idx, coef, mul, N, 3, S, S, 8, st);
+    }
+    conv_bwd_w(T, L0, O.XB[0], Q.XB[0], P.X0, nullptr, dw, dw_t, gout, st);
+    flush_w(st, MAIN_TAIL);
+    join(st);
+    launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw,
+                       T ? dw_t : nullptr, gout, st);
+    POST_WALK("reg_backward");
+    return 0;
+  }
+
   // ------------------------------------------------------------------ image encoder: F / T-fwd
   int img_forward(bool T, int slot, const float* th, const float* th_t, const float* image,
                   const int64_t* idx, float* feat_out, hipStream_t st) override {
@@ -1352,7 +1589,8 @@ struct Eng : mdd_engine {
     CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
     select_prec(T, false);
     if (is_vit) return vit_forward(T, slot, th, th_t, image, idx, feat_out, st);
-    if (nf.stem_pool) return res_forward(T, slot, th, th_t, image, idx, feat_out, st);
+    if (walker == 1) return res_forward(T, slot, th, th_t, image, idx, feat_out, st);
+    if (walker == 2) return reg_forward(T, slot, th, th_t, image, idx, feat_out, st);
     ActSet& P = sets[slot]; ActSet& Q = tn;
     int nb = (int)blks.size();
     launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
@@ -1437,7 +1675,8 @@ struct Eng : mdd_engine {
     CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
     select_prec(T, true);
     if (is_vit) return vit_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
-    if (nf.stem_pool) return res_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+    if (walker == 1) return res_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+    if (walker == 2) return reg_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
     ActSet& P = sets[slot]; ActSet& Q = tn;
     ActSet& O = (!T && !stash) ? tn : P;  // where primal backward signals are written
     int nb = (int)blks.size();
@@ -1743,6 +1982,12 @@ int mdd_set_pipe_kernels(int enable) {
   return prev;
 }
 
+int mdd_set_group8_kernels(int enable) {
+  const int prev = group8_kernels_mode();
+  set_group8_kernels(enable);
+  return prev;
+}
+
 int mdd_engine_create(const mdd_config* cfg, mdd_engine** out) {
   CHECK_ARG(cfg && out && cfg->variant, "null config");
   *out = nullptr;
@@ -2022,6 +2267,33 @@ int mdd_op_maxpool2d_3s2(int dtype, int mode, int n, int h, int w, int c, const 
     else launch_maxpool3s2_bwd<bf16>((bf16*)y, (const bf16*)x, ix, n, h, w, c, st);
   }
   POST_LAUNCH("op_maxpool2d_3s2");
+  return 0;
+}
+
+int mdd_op_mid_se(int dtype, int mode, int n, int hw, int c, float ga, const void* c2, const void* c2_t, const float* gate,
+                  const float* gate_t, const void* a3bar, const void* a3bar_t, const float* qbar, void* out, void* out_t,
+                  float* zbar, float* zbar_t, void* stream) {
+  CHECK_ARG(c2 && gate && out, "null pointer");
+  CHECK_ARG(n > 0 && hw > 0 && c > 0, "empty problem");
+  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype must be MDD_DTYPE_F32 or MDD_DTYPE_BF16");
+  CHECK_ARG(mode == 0 || mode == 1, "mode must be 0 (forward) or 1 (backward)");
+  CHECK_ARG(c % (dtype == MDD_DTYPE_F32 ? 4 : 8) == 0, "channels must be a multiple of the 16-byte chunk");
+  const bool T = c2_t != nullptr;
+  CHECK_ARG(T == (gate_t != nullptr) && T == (out_t != nullptr), "tangent operands come together");
+  CHECK_ARG(mode == 0 || (a3bar && zbar && T == (a3bar_t != nullptr) && T == (zbar_t != nullptr)), "backward operands");
+  hipStream_t st = (hipStream_t)stream;
+  auto run = [&](auto* tag) {
+    using AT = std::remove_pointer_t<decltype(tag)>;
+    if (mode == 0) {
+      launch_mid_se_apply<AT>((AT*)out, (AT*)out_t, (const AT*)c2, (const AT*)c2_t, gate, gate_t, ga, n, hw, c, st);
+    } else {
+      launch_mid_se_bwd<AT>(zbar, zbar_t, (AT*)out, (AT*)out_t, (const AT*)c2, (const AT*)c2_t, (const AT*)a3bar,
+                            (const AT*)a3bar_t, gate, gate_t, ga, n, hw, c, st);
+      if (qbar) launch_add_pooled<AT>(T ? (AT*)out_t : (AT*)out, qbar, 1.f / (float)hw, n, hw, c, st);
+    }
+  };
+  if (dtype == MDD_DTYPE_F32) run((float*)nullptr); else run((bf16*)nullptr);
+  POST_LAUNCH("op_mid_se");
   return 0;
 }
 

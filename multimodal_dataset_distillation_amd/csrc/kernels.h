@@ -102,6 +102,14 @@ void launch_conv_gemm_relu(const ConvGeom& g, const AT* A1, const AT* B1, const 
 bool pipe_kernels_enabled();
 void set_pipe_kernels(bool on);   // ConvEpi::act == 1 may be requested for this geometry
 
+// ---------------------------------------------------------------- conv_g8.hip (bf16; grouped 3x3, 8 channels per group)
+// launch_conv_gemm tries this first; false = geometry, epilogue or pass not taken (or switched off:
+// mdd_set_group8_kernels), the caller goes on to the general kernels.  Same operand and epilogue contracts.
+int group8_kernels_mode();              // 0 off, 1 the measured routes (default), 2 every geometry
+void set_group8_kernels(int mode);
+bool launch_conv_g8(const ConvGeom& g, const bf16* A1, const bf16* B1, const bf16* A2, const bf16* B2, const ConvEpi& ep,
+                    hipStream_t st);
+
 // ---------------------------------------------------------------- conv_wgrad.hip
 // dW[g][co][tap][kc] = sum_m dy[m][g*nc+co] * x[src(m,tap)][g*kc+kc], split over M.
 //   slab != null (slab_floats >= the layer's dW size): two-phase combine -- partial tiles by plain
@@ -198,6 +206,25 @@ void launch_im2col(AT* col, const AT* in, int n, int h, int w, int cpad, int k, 
 // out = alpha*in  (elems a multiple of the 16-byte chunk)
 template <class AT>
 void launch_scale_act(AT* out, const AT* in, float alpha, int64_t elems, hipStream_t st);
+
+// ---------------------------------------------------------------- nfreg.hip (NF-RegNet image path)
+// mid-block squeeze-excite: a3 = silu(ga * gate * c2)   (tangent when c2_t is non-null: writes a3_t only)
+template <class AT>
+void launch_mid_se_apply(AT* a3, AT* a3_t, const AT* c2, const AT* c2_t, const float* gate, const float* gate_t, float ga,
+                         int n, int hw, int c, hipStream_t st);
+// its backward in one pass over (c2, a3bar): c2bar = ga*gate*dsilu(u)*a3bar with u = ga*gate*c2 (the direct share; the
+// pooled path's is added by launch_add_pooled) and zbar[n,c] = (ga * sum_hw c2*dsilu(u)*a3bar) * gate*(1-gate)
+template <class AT>
+void launch_mid_se_bwd(float* zbar, float* zbar_t, AT* c2bar, AT* c2bar_t, const AT* c2, const AT* c2_t, const AT* a3bar,
+                       const AT* a3bar_t, const float* gate, const float* gate_t, float ga, int n, int hw, int c,
+                       hipStream_t st);
+// x[n, hw, c] += v[n, c] * mul
+template <class AT>
+void launch_add_pooled(AT* x, const float* v, float mul, int n, int hw, int c, hipStream_t st);
+// X' = alpha*C3 + SC ; A' = beta*silu(X')  (ao / ao_t may be null; tangent when c3_t is non-null: writes tangents only)
+template <class AT>
+void launch_resid_silu(const AT* c3, const AT* c3_t, const AT* sc, const AT* sc_t, AT* xo, AT* xo_t, AT* ao, AT* ao_t,
+                       float alpha, float beta, int64_t elems, hipStream_t st);
 
 // ---------------------------------------------------------------- linear.hip (fp32, small M)
 // Split-K scratch of the small-M SGEMM: per-tile accumulators, bias-gradient row sums and arrival

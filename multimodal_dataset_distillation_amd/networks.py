@@ -26,10 +26,13 @@ from . import functional as Fn
 # 'vit_tiny16' (headless, 192-d class token) and 'vit_b16' (BASELINE configs[4]'s ViT-B/16; the reference's 'clip' is
 # ViT-B/32 through the clip package) are build-defined.  'nf_resnet50' is timm.create_model('nf_resnet50', pretrained=True)
 # (networks.py:669-670), also with its 1000-way head: 1000-d features; 'nf_resnet_tiny' is its build-defined miniature.
+# 'nf_regnet' is timm.create_model('nf_regnet_b1', pretrained=True) (networks.py:671-672), head kept as well: 1000-d
+# features; 'nf_regnet_tiny' is its build-defined miniature.
 VARIANTS = {"nfnet": "nfnet_l0", "nfnet_l0": "nfnet_l0", "nfnet_l1": "nfnet_l1",
             "nfnet_tiny": "nfnet_tiny", "vit": "vit_tiny16_cls", "vit_tiny16_cls": "vit_tiny16_cls",
             "vit_tiny16": "vit_tiny16", "vit_b16": "vit_b16", "vit_micro": "vit_micro", "vit_micro_cls": "vit_micro_cls",
-            "nf_resnet50": "nf_resnet50", "nf_resnet_tiny": "nf_resnet_tiny"}
+            "nf_resnet50": "nf_resnet50", "nf_resnet_tiny": "nf_resnet_tiny",
+            "nf_regnet": "nf_regnet_b1", "nf_regnet_b1": "nf_regnet_b1", "nf_regnet_tiny": "nf_regnet_tiny"}
 
 _ENGINES = {}
 
@@ -72,7 +75,7 @@ def _attach(root, dotted, param):
 
 def init_image_params(table, generator=None, trained_like=False):
     """timm NormFreeNet init: kaiming_normal_(fan_in, linear) conv weights, zero bias, gain 1 (conv3:
-    0); a classifier (NF-ResNet's head.fc): normal(0, 0.01) weight, zero bias.  trained_like=True perturbs
+    0; the squeeze-excite fc1 / fc2 are plain convs); a classifier (NF-ResNet's and NF-RegNet's head.fc): normal(0, 0.01) weight, zero bias.  trained_like=True perturbs
     gains/biases the way oracle/nfnet_ref.randomize_like_trained does (synthetic expert snapshots; default
     init zeroes most of the theta-gradient)."""
     out = []
