@@ -66,9 +66,9 @@ typedef struct mdd_config {
 
 const char* mdd_last_error(void);
 /* ABI version of this header: 2 = round 2 (mdd_config.keep_steps, MDD_DTYPE_BF16X2 / _F32_BF16OPS,
- * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se.  A binding built against another version
+ * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se; 9 = + mdd_set_se_fused.  A binding built against another version
  * must refuse to load. */
-#define MDD_ABI_VERSION 8
+#define MDD_ABI_VERSION 9
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
  * pipelined kernels; 0 routes them to the general kernels instead (process-wide; returns the previous setting).  For the
@@ -79,6 +79,11 @@ int mdd_set_pipe_kernels(int enable);
  * the general kernels, 2 routes every such geometry to the dedicated kernel (process-wide; returns the previous setting).
  * For the parity tests, which run the same geometry both ways, and for A/B timing. */
 int mdd_set_group8_kernels(int enable);
+/* The NFNet image walker applies the squeeze-excite gate, the residual add and the next pre-activation in conv3's forward
+ * epilogue (1, the default); 0 = conv3 writes C3 and a separate elementwise kernel applies the gate (process-wide; returns
+ * the previous setting).  Both give the same bits in the forward passes.  For the parity tests, which run a pass both
+ * ways, and for A/B timing. */
+int mdd_set_se_fused(int enable);
 
 /* ---- engine lifetime and memory (the caller owns device memory: PyTorch caching allocator) */
 int mdd_engine_create(const mdd_config* cfg, mdd_engine** out);

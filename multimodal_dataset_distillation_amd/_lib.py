@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmdd_hip.so")
 
 DTYPE_F32, DTYPE_BF16, DTYPE_BF16X2, DTYPE_F32_BF16OPS = 0, 1, 2, 3
-ABI_VERSION = 8     # include/mdd_hip.h MDD_ABI_VERSION
+ABI_VERSION = 9     # include/mdd_hip.h MDD_ABI_VERSION
 
 
 class MddConfig(C.Structure):
@@ -68,6 +68,7 @@ SIGNATURES = {
     "mdd_op_conv2d_wgrad": (_I, [_I] * 10 + [_P, _P, _P, _P, _P]),
     "mdd_set_pipe_kernels": (_I, [_I]),
     "mdd_set_group8_kernels": (_I, [_I]),
+    "mdd_set_se_fused": (_I, [_I]),
     "mdd_op_conv2d_wgrad2": (_I, [_I] * 10 + [_P] * 7 + [C.c_longlong, _P]),
     "mdd_op_maxpool2d_3s2": (_I, [_I] * 6 + [_P] * 4),
     "mdd_op_mid_se": (_I, [_I] * 5 + [_F] + [_P] * 12),

@@ -186,7 +186,28 @@ template <int ACT> DEVI Dual dactf(Dual x) {
   else if constexpr (ACT == 2) return dgelu_fast_(x); else if constexpr (ACT == 1) return dgelu_(x); else return dsilu_(x);
 }
 
-template <class AT, int WGM, int WGN, int TM, int TN, int MODE, bool KFULL, int PREC, bool IBK = false, int ACT = 0>
+// The squeeze-excite apply of the conv3 epilogues (conv_gemm_epilogue_se.inc), one element: X' = C3 * g + SC with
+// g = gate * ga, A' = beta * silu(X'), primal and tangent (the Dual rule of k_se_apply_tiled, elementwise.hip).  Which
+// products the compiler fuses into multiply-adds is its choice per kernel, and a different choice in this epilogue than in
+// the elementwise kernel moved every tangent downstream by an ulp: the multiply-adds are written out here where the
+// elementwise kernel has them (fma(c, g, sc); fma(c_t, g, c * g_t) + sc_t; s * fma(x, 1 - s, 1)), contraction is off for
+// the rest, and the forward passes give the same bits with the apply fused or separate (tests/test_gpu_se_fused.py).
+DEVI void se_apply_primal(float c, float g, float sc, float beta, float& xo, float& ao) {
+#pragma clang fp contract(off)
+  xo = __builtin_fmaf(c, g, sc);
+  ao = silu_(xo) * beta;
+}
+DEVI void se_apply_tangent(float c, float c_t, float g, float g_t, float sc, float sc_t, float beta, float& xo_t,
+                           float& ao_t) {
+#pragma clang fp contract(off)
+  const float x = __builtin_fmaf(c, g, sc);
+  xo_t = __builtin_fmaf(c_t, g, c * g_t) + sc_t;
+  const float s = sigmoidf_(x);
+  ao_t = beta * (xo_t * (s * __builtin_fmaf(x, 1.f - s, 1.f)));
+}
+
+template <class AT, int WGM, int WGN, int TM, int TN, int MODE, bool KFULL, int PREC, bool IBK = false, int ACT = 0,
+          bool SEK = false>
 __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p) {
   constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
   constexpr int RA = BM / 32, RB = BN / 32;
@@ -570,9 +591,13 @@ __global__ __launch_bounds__(256, MDD_MIN_WAVES) void k_conv_gemm(const KArgs p)
     __syncthreads();
   }
 
+  if constexpr (SEK) {   // conv3 with the squeeze-excite apply: instances of their own, holding only those two epilogues
+#include "conv_gemm_epilogue_se.inc"
+  } else {
 #define MDD_EPI_HOISTED 0
 #include "conv_gemm_epilogue.inc"
 #undef MDD_EPI_HOISTED
+  }
 }
 
 
@@ -740,14 +765,17 @@ __global__ __launch_bounds__(512, 1) void k_gemm_pipe(const KArgs p) {
 #undef MDD_EPI_HOISTED
 }
 
+// the shapes k_gemm_pipe takes (bf16 storage; M = output rows)
+bool pipe_gemm_shape(const ConvGeom& g, int M) {
+  const bool pw = g.k == 1 && g.stride == 1 && g.pad == 0 && g.groups == 1;
+  return pipe_kernels_enabled() && pw && g.prec == 0 && g.kc >= MDD_PIPE_MIN && g.nc >= MDD_PIPE_MIN && !(g.kc & 63) &&
+         !(g.nc & 7) && !(g.ca_tot & 7) && !(g.co_tot & 7) && M >= 8192 && (int64_t)M * g.ca_tot * 2 < (1ll << 31) &&
+         (int64_t)g.nc * g.kc * 2 < (1ll << 31);
+}
 // false = shape not taken (the caller goes on to the one-stage kernel)
 bool launch_pipe_gemm(const KArgs& a, hipStream_t st) {
   const ConvGeom& g = a.g;
-  const bool pw = g.k == 1 && g.stride == 1 && g.pad == 0 && g.groups == 1;
-  if (!pipe_kernels_enabled() || !pw || g.prec != 0 || g.kc < MDD_PIPE_MIN || g.nc < MDD_PIPE_MIN || (g.kc & 63) || (g.nc & 7) || (g.ca_tot & 7) ||
-      (g.co_tot & 7) || a.M < 8192 || a.ep.ib != nullptr || (int64_t)a.M * g.ca_tot * 2 >= (1ll << 31) ||
-      (int64_t)g.nc * g.kc * 2 >= (1ll << 31))
-    return false;
+  if (!pipe_gemm_shape(g, a.M) || a.ep.ib != nullptr) return false;
   KArgs k = a;
   k.mtiles = (a.M + 255) / 256;
   k.ntiles = (g.nc + 255) / 256;
@@ -769,7 +797,8 @@ bool launch_pipe_gemm(const KArgs& a, hipStream_t st) {
 }
 #endif  // MDD_CONV_GEMM_RELU_TU
 
-template <class AT, int WGM, int WGN, int TM, int TN, int MODE, bool KFULL, int PREC, bool IBK = false, int ACT = 0>
+template <class AT, int WGM, int WGN, int TM, int TN, int MODE, bool KFULL, int PREC, bool IBK = false, int ACT = 0,
+          bool SEK = false>
 void launch_cfg(const KArgs& a, hipStream_t st) {
   constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
   KArgs k = a;
@@ -786,13 +815,13 @@ void launch_cfg(const KArgs& a, hipStream_t st) {
   (void)hipGetDevice(&dev);
   const uint64_t bit = 1ull << (dev & 63);
   if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_conv_gemm<AT, WGM, WGN, TM, TN, MODE, KFULL, PREC, IBK, ACT>,
+    hipError_t e = hipFuncSetAttribute((const void*)k_conv_gemm<AT, WGM, WGN, TM, TN, MODE, KFULL, PREC, IBK, ACT, SEK>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                        MODE == 4 ? (int)MODE4_MAX_LDS : (int)shm);
     if (e == hipSuccess) attr_devs.fetch_or(bit, std::memory_order_release);
   }
   int64_t blocks = (int64_t)k.mtiles * k.ntiles * a.g.groups;
-  k_conv_gemm<AT, WGM, WGN, TM, TN, MODE, KFULL, PREC, IBK, ACT><<<(unsigned)blocks, 256, shm, st>>>(k);
+  k_conv_gemm<AT, WGM, WGN, TM, TN, MODE, KFULL, PREC, IBK, ACT, SEK><<<(unsigned)blocks, 256, shm, st>>>(k);
 }
 
 // ACTV = 0: every launch but the ReLU epilogues (SiLU / GELU / no activation); ACTV = 3: the ReLU epilogues (their own
@@ -849,6 +878,12 @@ void launch_conv_gemm_(const ConvGeom& g, const AT* A1, const AT* B1, const AT* 
     MDD_DISPATCH_P(WGM, WGN, TM, TN, 0);                                                      \
   } while (0)
 #ifndef MDD_CONV_GEMM_RELU_TU
+  if (ep.mode == EPI_FWD_SE || ep.mode == EPI_FWD_SE_T) {
+    // conv3 with the squeeze-excite apply (the caller has asked conv_gemm_supports_se): the 128 x 128 pointwise kernel
+    if (kfull) launch_cfg<AT, 2, 2, 2, 2, 0, true, 0, false, 0, true>(a, st);
+    else launch_cfg<AT, 2, 2, 2, 2, 0, false, 0, false, 0, true>(a, st);
+    return;
+  }
   if constexpr (sizeof(AT) == 2) {
     if (launch_pipe_gemm(a, st)) return;
   }
@@ -890,6 +925,15 @@ bool pipe_kernels_enabled() { return g_pipe_on.load(std::memory_order_relaxed) !
 void set_pipe_kernels(bool on) { g_pipe_on.store(on ? 1 : 0, std::memory_order_relaxed); }
 bool conv_gemm_supports_gelu(const ConvGeom& g) {
   return g.k == 1 && g.stride == 1 && g.pad == 0 && g.groups == 1 && g.nc > 64;
+}
+bool conv_gemm_supports_se(const ConvGeom& g, int esize) {
+  const bool pw = g.k == 1 && g.stride == 1 && g.pad == 0 && g.groups == 1;
+  const int ce = 16 / esize;
+  // a conv3 that k_gemm_pipe runs today stays there, with the separate apply kernel: the fused epilogue exists in the
+  // one-stage 128 x 128 kernel only, and which of the two is faster on such a shape has not been measured
+  const bool pipe = esize == 2 && pipe_gemm_shape(g, g.nimg * g.ho * g.wo);
+  return pw && g.nc > 64 && g.prec == 0 && !g.transposed && !pipe && g.nc % ce == 0 && g.co_tot % ce == 0 &&
+         (int64_t)g.nimg * g.ho * g.wo * g.co_tot < (1ll << 31);
 }
 template void launch_conv_gemm<float>(const ConvGeom&, const float*, const float*, const float*,
                                       const float*, const ConvEpi&, hipStream_t);

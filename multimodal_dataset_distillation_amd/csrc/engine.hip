@@ -17,6 +17,7 @@
 #include <cstring>
 #include <type_traits>
 #include <algorithm>
+#include <atomic>
 #include <string>
 #include <functional>
 #include <vector>
@@ -26,6 +27,9 @@
 
 // ------------------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
+// mdd_set_se_fused: the squeeze-excite apply in conv3's forward epilogue (NFNet walker)
+static std::atomic<int> g_se_fused{1};
+static bool se_fused_enabled() { return g_se_fused.load(std::memory_order_relaxed) != 0; }
 int mdd_set_error(hipError_t e, const char* what) {
   char buf[512];
   snprintf(buf, sizeof buf, "HIP error %d (%s) at %s%s", (int)e, hipGetErrorString(e), what,
@@ -918,7 +922,8 @@ struct Eng : mdd_engine {
     p.flops = 2.0 * conv_macs(L) * ns;
     double ain = (double)g.nimg * g.ha * g.wa * g.ca_tot, aout = (double)g.nimg * g.ho * g.wo * g.co_tot;
     int nio = (e.out_raw ? 1 : 0) + (e.out_act ? 1 : 0) + (e.c ? 1 : 0) + (e.c_t ? 1 : 0) +
-              (e.abar ? 1 : 0) + (e.add1 ? 1 : 0) + (e.add2 ? 1 : 0);
+              (e.abar ? 1 : 0) + (e.add1 ? 1 : 0) + (e.add2 ? 1 : 0) +
+              ((e.mode == EPI_FWD_SE || e.mode == EPI_FWD_SE_T) && e.out_x ? 1 : 0);   // (+ the shortcut: add1 / add2)
     p.bytes = (ain * ns + (double)L.packed() * ns + aout * nio) * sizeof(AT);
     ck(hipEventCreate(&p.a), "hipEventCreate"); ck(hipEventCreate(&p.b), "hipEventCreate");
     ck(hipEventRecord(p.a, st), "hipEventRecord");
@@ -1631,10 +1636,13 @@ struct Eng : mdd_engine {
       // the pooled MID-channel activation: p = W3_hat q + b3 with q = mean_hw(A2b) -- a quarter of the bytes of
       // pooling C3, and the whole gate chain (pool, three small-batch linears) no longer waits for conv3: it runs
       // on the side stream beside it and meets the main stream at the SE apply.
+      // (with the apply fused into conv3's epilogue, below, conv3 waits for the gate anyway: the chain then runs on the
+      // main stream in front of it and the two cross-stream events of the block are saved)
+      const bool fuse3 = se_fused_enabled() && conv_gemm_supports_se(gfwd(convs[B.c3]), (int)sizeof(AT));
       bool g_forked = false;
       {
         hipStream_t gs = st;
-        if (use_side && gstream) { fork_to(gstream, st); gs = gstream; g_forked = true; }
+        if (use_side && gstream && !fuse3) { fork_to(gstream, st); gs = gstream; g_forked = true; }
         launch_pool_mean<AT>(T ? qa.q : pa.q, T ? qa.A2b : pa.A2b, N, hw, B.mid, gs);
         const ConvL& L3 = convs[B.c3];
         launch_linear_fwd_w<AT>(pa.p, T ? qa.p : nullptr, pa.q, T ? qa.q : nullptr, wf + L3.off_p,
@@ -1647,8 +1655,31 @@ struct Eng : mdd_engine {
                           T ? th_t + B.se.off_w2 : nullptr, th + B.se.off_b2,
                           T ? th_t + B.se.off_b2 : nullptr, N, rd, c, 2, lin_main, gs);
       }
-      conv_fwd(T, convs[B.c3], pa.A2b, qa.A2b, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
       bool lastb = b == nb - 1;
+      const ConvL& L3f = convs[B.c3];
+      if (fuse3) {
+        // the gate no longer depends on conv3, so conv3's epilogue applies it: C3 is stashed as before, and X' (and the
+        // next block's pre-activation A') are written from the accumulator tile instead of by a second kernel that
+        // re-reads C3.  conv3 now waits for the gate chain (in front of it on this stream) and for the shortcut, which
+        // its epilogue reads.
+        if (sc_forked) join(st);
+        ConvGeom g = gfwd(L3f);
+        ConvEpi e; memset(&e, 0, sizeof e);
+        e.beta = lastb ? 1.f : blks[b + 1].beta;
+        e.ib = pa.gate; e.ib_t = T ? qa.gate : nullptr; e.ib_mul = ga; e.ib_hw = hw;
+        e.add1 = sc; e.add2 = T ? sc_t : nullptr;
+        if (!T) {
+          e.mode = EPI_FWD_SE; e.bias = th + L3f.off_b; e.out_raw = pa.C3; e.out_x = P.X[b + 1];
+          e.out_act = lastb ? nullptr : P.A[b + 1];
+          gemm(L3f, g, pa.A2b, wf + L3f.off_p, nullptr, nullptr, e, st);
+        } else {
+          e.mode = EPI_FWD_SE_T; e.bias_t = th_t + L3f.off_b; e.c = pa.C3; e.out_raw = qa.C3; e.out_x = Q.X[b + 1];
+          e.out_act = lastb ? nullptr : Q.A[b + 1];
+          gemm(L3f, g, qa.A2b, wf + L3f.off_p, pa.A2b, wf_t + L3f.off_p, e, st);
+        }
+        continue;
+      }
+      conv_fwd(T, convs[B.c3], pa.A2b, qa.A2b, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
       if (sc_forked) join(st);
       if (g_forked) join_from(gstream, st);
       launch_se_apply<AT>(pa.C3, T ? qa.C3 : nullptr, pa.gate, T ? qa.gate : nullptr, sc,
@@ -1981,6 +2012,8 @@ int mdd_set_pipe_kernels(int enable) {
   set_pipe_kernels(enable != 0);
   return prev;
 }
+
+int mdd_set_se_fused(int enable) { return g_se_fused.exchange(enable != 0 ? 1 : 0, std::memory_order_relaxed); }
 
 int mdd_set_group8_kernels(int enable) {
   const int prev = group8_kernels_mode();

@@ -69,6 +69,9 @@ struct ConvEpi {
   float ib_mul;
   int ib_hw;
   int act;                // activation of the fused chain rule: 0 SiLU, 1 exact GELU (conv_gemm_supports_gelu), 3 ReLU
+  // squeeze-excite apply modes (EPI_FWD_SE / _T, conv_gemm_supports_se): x' (or its tangent) goes to out_x; the gate is
+  // ib / ib_t ([nimg, co_tot] fp32, image = m / ib_hw), ga is ib_mul, the shortcut is add1 and its tangent add2
+  void* out_x;            // AT*
 };
 enum {
   EPI_FWD = 0,        // c = acc + bias ; out_raw = c ; out_act = beta*silu(c)
@@ -76,6 +79,9 @@ enum {
   EPI_BWD = 2,        // a = acc + add1 ; out_raw = a ; out_act = beta*dsilu(c)*a + add2
   EPI_BWD_T = 3,      // a = Dual(abar, acc + add1); out_act = (beta*dsilu(Dual(c,c_t))*a).t + add2
   EPI_BWD_LIN = 4,    // a = acc + add1 ; out_raw = a     (no activation in between)
+  // conv3 of an NFNet block with the squeeze-excite apply, the residual add and the next pre-activation (c' = c as stored):
+  EPI_FWD_SE = 5,     // c = acc + bias ; out_raw = c ; x = c'*(gate*ga) + sc ; out_x = x ; out_act = beta*silu(x)
+  EPI_FWD_SE_T = 6,   // the same rule on Dual(c, acc + bias_t), Dual(gate, gate_t), Dual(sc, sc_t): the tangents are stored
 };
 struct ConvGeom {
   int nimg;
@@ -92,6 +98,9 @@ template <class AT>
 void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
                       const ConvEpi& ep, hipStream_t st);
 bool conv_gemm_supports_gelu(const ConvGeom& g);
+// EPI_FWD_SE / EPI_FWD_SE_T may be requested for this geometry (pointwise, the 128 x 128 tile, exact arithmetic of the
+// storage type, not a shape of the pipelined kernel); esize = sizeof the storage type
+bool conv_gemm_supports_se(const ConvGeom& g, int esize);
 // ConvEpi::act == 3 (ReLU) with an activation output: the ReLU instances (conv_gemm_relu.hip); launch_conv_gemm
 // forwards such launches itself
 template <class AT>

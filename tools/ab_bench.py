@@ -32,6 +32,8 @@ def one(lib_path, dtype, steps, workload, own_stream=False):
     lib = _lib.load()
     if os.environ.get("AB_NO_PIPE"):          # A/B of the 256 x 256 pipelined kernels inside one build
         lib.mdd_set_pipe_kernels(0)
+    if os.environ.get("AB_SE_FUSED") is not None:   # A/B of the squeeze-excite apply in conv3's epilogue inside one build
+        lib.mdd_set_se_fused(int(os.environ["AB_SE_FUSED"]))
     g = torch.Generator().manual_seed(0)
     image_syn = torch.randn(n, 3, size, size, generator=g).to(dev)
     text_syn = (torch.randn(n, d_txt, generator=g) * 0.5253).to(dev)
