@@ -66,9 +66,9 @@ typedef struct mdd_config {
 
 const char* mdd_last_error(void);
 /* ABI version of this header: 2 = round 2 (mdd_config.keep_steps, MDD_DTYPE_BF16X2 / _F32_BF16OPS,
- * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se; 9 = + mdd_set_se_fused.  A binding built against another version
+ * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se; 9 = + mdd_set_se_fused; 10 = + mdd_op_linear, mdd_op_pool_se.  A binding built against another version
  * must refuse to load. */
-#define MDD_ABI_VERSION 9
+#define MDD_ABI_VERSION 10
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
  * pipelined kernels; 0 routes them to the general kernels instead (process-wide; returns the previous setting).  For the
@@ -242,6 +242,43 @@ int mdd_op_maxpool2d_3s2(int dtype, int mode, int n, int h, int w, int c, const 
 int mdd_op_mid_se(int dtype, int mode, int n, int hw, int c, float ga, const void* c2, const void* c2_t, const float* gate,
                   const float* gate_t, const void* a3bar, const void* a3bar_t, const float* qbar, void* out, void* out_t,
                   float* zbar, float* zbar_t, void* stream);
+
+/* The small-batch linear layers (csrc/linear.hip): squeeze-excite fc1 / fc2, the pooled-feature -> conv3 shortcut, the
+ * text head.  n = batch, k = in features, j = out features; x [n, k], W [j, k], b [j], dy [n, j], all fp32 row-major
+ * (form 3: W in wdtype).  A call is a TANGENT call when out_t is given (forms 0, 1, 3) or when dy_t or x_t is given
+ * (forms 2, 4); it writes the tangent result only, and every tangent operand may be null on its own (= 0).
+ *   form 0  forward:  out = y [n, j] = act(x W^T + b), act 0 none / 1 ReLU / 2 sigmoid, b may be null.
+ *           tangent: out holds the stashed post-activation y (an input), out_t = act'(y) * (x_t W^T + x W_t^T + b_t)
+ *   form 1  dgrad:    out = dx [n, k] = dy W, times [relu_of [n, k] > 0] when relu_of is given
+ *           tangent: out_t = (dy_t W + dy W_t), masked the same way
+ *   form 2  wgrad:    out = dW [j, k] = dy^T x, db [j] = column sums of dy (db may be null)
+ *           tangent: out = dy_t^T x + dy^T x_t, db = column sums of dy_t
+ *   form 3  typed-weight forward: out = alpha * (x W^T) + b with W (and W_t) in wdtype = MDD_DTYPE_F32 or _BF16
+ *           tangent: out_t = alpha * (x_t W^T + x W_t^T) + b_t
+ *   form 4  form 2, ADDED into out and db
+ * route 0 = the engine's route (the one-workgroup-per-tile matrix-core kernel); route 1 = the route retrieval and the
+ * caption decode take (no scratch: the LDS-tiled kernel, unsplit) -- form 0 only, primal, act 0, no bias.
+ * wdtype is MDD_DTYPE_F32 except in form 3; alpha is read by form 3 only. */
+int mdd_op_linear(int form, int route, int wdtype, int n, int k, int j, int act, float alpha, const float* x,
+                  const float* x_t, const void* W, const void* W_t, const float* b, const float* b_t, const float* dy,
+                  const float* dy_t, const float* relu_of, float* out, float* out_t, float* db, void* stream);
+
+/* The pooled / squeeze-excite kernels of the NFNet image path (csrc/elementwise.hip).  Activations are NHWC
+ * [n, h, w, c] in the storage type (dtype = MDD_DTYPE_F32 or _BF16; c a multiple of 4 or 8), hw = h * w; the per-(image,
+ * channel) operand v and the pooled outputs are [n, c] fp32.  Tangent operands (`_t`) come all together or not at all;
+ * with them ONLY the `_t` outputs are written.
+ *   op 0  out [n, c] fp32 = mean_hw a                                            (linear: no tangent form)
+ *   op 1  out [n, c] fp32 = mean_hw silu(a) ;  op 2  the same with relu          (tangent: out_t)
+ *   op 3  out = v / hw * dsilu(a), v = the gradient of op 1's output ;  op 4  v / hw * [a > 0]      (tangent: out_t)
+ *   op 5  a = c3, b = sc, v = gate: out = x' = c3 * gate * ga + sc, out2 = beta * silu(x') (out2 may be null)
+ *         (tangent: out_t, out2_t)
+ *   op 6  a = xbar, b = c3, v = gate: out [n, c] fp32 = zbar = (ga * sum_hw xbar * c3) * gate * (1 - gate),
+ *         out2 = c3bar = xbar * gate * ga                                          (tangent: out_t, out2_t)
+ *   op 7  AvgPool2d(2, 2, ceil_mode, count_include_pad = False): a [n, h, w, c] -> out [n, ceil(h/2), ceil(w/2), c]
+ *   op 8  its backward: a = dout [n, ceil(h/2), ceil(w/2), c] -> out = din [n, h, w, c]          (7, 8: no tangent form) */
+int mdd_op_pool_se(int dtype, int op, int n, int h, int w, int c, float ga, float beta, const void* a, const void* a_t,
+                   const void* b, const void* b_t, const float* v, const float* v_t, void* out, void* out_t, void* out2,
+                   void* out2_t, void* stream);
 
 /* ---- synthetic-set evaluation: retrieval ranks.
  * Replaces the per-row host loops of reference epoch.py:140-156 (image->text: argsort of one similarity

@@ -2330,6 +2330,79 @@ int mdd_op_mid_se(int dtype, int mode, int n, int hw, int c, float ga, const voi
   return 0;
 }
 
+int mdd_op_linear(int form, int route, int wdtype, int n, int k, int j, int act, float alpha, const float* x,
+                  const float* x_t, const void* W, const void* W_t, const float* b, const float* b_t, const float* dy,
+                  const float* dy_t, const float* relu_of, float* out, float* out_t, float* db, void* stream) {
+  CHECK_ARG(form >= 0 && form <= 4, "form must be 0 (forward), 1 (dgrad), 2 (wgrad), 3 (typed forward) or 4 (wgrad, accumulating)");
+  CHECK_ARG(route == 0 || route == 1, "route must be 0 (engine) or 1 (retrieval)");
+  CHECK_ARG(n > 0 && k > 0 && j > 0, "empty problem");
+  CHECK_ARG(out, "null output");
+  CHECK_ARG(wdtype == MDD_DTYPE_F32 || (form == 3 && wdtype == MDD_DTYPE_BF16), "weights are fp32 (form 3: fp32 or bf16)");
+  CHECK_ARG(act >= 0 && act <= 2 && (form == 0 || act == 0), "act is 0, 1 or 2, and belongs to form 0");
+  CHECK_ARG(route == 0 || (form == 0 && act == 0 && !b && !out_t), "route 1 is the plain primal forward");
+  hipStream_t st = (hipStream_t)stream;
+  LinScratch ws;           // route 1: no scratch, as retrieval.hip passes it
+  if (route == 0) ws.mfma = true;   // what lin_scratch_carve gives the engine (the matrix-core kernel uses no scratch)
+  const float* Wf = (const float*)W;
+  const float* Wf_t = (const float*)W_t;
+  if (form == 0 || form == 3) {
+    CHECK_ARG(x && W, "forward operands");
+    CHECK_ARG(out_t || !(x_t || W_t || b_t), "tangent operands without a tangent output");
+    if (form == 0) launch_linear_fwd(out, out_t, x, x_t, Wf, Wf_t, b, b_t, n, k, j, act, ws, st);
+    else if (wdtype == MDD_DTYPE_F32) launch_linear_fwd_w<float>(out, out_t, x, x_t, Wf, Wf_t, b, b_t, n, k, j, alpha, st);
+    else launch_linear_fwd_w<bf16>(out, out_t, x, x_t, (const bf16*)W, (const bf16*)W_t, b, b_t, n, k, j, alpha, st);
+  } else if (form == 1) {
+    CHECK_ARG(dy && W, "dgrad operands");
+    CHECK_ARG(out_t || !(dy_t || W_t), "tangent operands without a tangent output");
+    launch_linear_dgrad(out, out_t, dy, dy_t, Wf, Wf_t, relu_of, n, k, j, ws, st);
+  } else {
+    CHECK_ARG(dy && x && !out_t, "wgrad operands (the tangent is written to out / db)");
+    if (form == 2) launch_linear_wgrad(out, db, dy, dy_t, x, x_t, n, k, j, ws, st);
+    else launch_linear_wgrad_accum(out, db, dy, dy_t, x, x_t, n, k, j, st);
+  }
+  POST_LAUNCH("op_linear");
+  return 0;
+}
+
+int mdd_op_pool_se(int dtype, int op, int n, int h, int w, int c, float ga, float beta, const void* a, const void* a_t,
+                   const void* b, const void* b_t, const float* v, const float* v_t, void* out, void* out_t, void* out2,
+                   void* out2_t, void* stream) {
+  CHECK_ARG(a && out, "null pointer");
+  CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0, "empty problem");
+  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype must be MDD_DTYPE_F32 or MDD_DTYPE_BF16");
+  CHECK_ARG(op >= 0 && op <= 8, "op");
+  CHECK_ARG(c % (dtype == MDD_DTYPE_F32 ? 4 : 8) == 0, "channels must be a multiple of the 16-byte chunk");
+  const bool T = a_t != nullptr;
+  const bool lin = op == 0 || op >= 7;           // linear in a: the tangent is the same call on a_t
+  CHECK_ARG(!lin || !(T || out_t), "ops 0, 7 and 8 have no tangent form");
+  CHECK_ARG(lin || T == (out_t != nullptr), "tangent operands come together");
+  CHECK_ARG(op < 3 || op > 6 || (v && T == (v_t != nullptr)), "the [n, c] operand");
+  CHECK_ARG(op < 5 || op > 6 || (b && T == (b_t != nullptr)), "the second activation operand");
+  CHECK_ARG(op != 5 || T || !out2_t, "se_apply: ao_t belongs to the tangent form");
+  CHECK_ARG(op != 6 || (out2 && T == (out2_t != nullptr)), "gate_grad: c3bar");
+  const int hw = h * w;
+  hipStream_t st = (hipStream_t)stream;
+  auto run = [&](auto* tag) {
+    using AT = std::remove_pointer_t<decltype(tag)>;
+    const AT *A = (const AT*)a, *A_t = (const AT*)a_t, *B = (const AT*)b, *B_t = (const AT*)b_t;
+    switch (op) {
+      case 0: launch_pool_mean<AT>((float*)out, A, n, hw, c, st); break;
+      case 1: case 2: launch_final_pool<AT>((float*)out, (float*)out_t, A, A_t, n, hw, c, st, op == 2); break;
+      case 3: case 4: launch_final_pool_bwd<AT>((AT*)out, (AT*)out_t, v, v_t, A, A_t, n, hw, c, st, op == 4); break;
+      case 5:   // the tangent form stores through ao_t alone: without it there is no activation output at all
+        launch_se_apply<AT>(A, A_t, v, v_t, B, B_t, (AT*)out, (AT*)out_t, (AT*)(T && !out2_t ? nullptr : out2),
+                            (AT*)out2_t, ga, beta, n, hw, c, st);
+        break;
+      case 6: launch_se_gate_grad_c3b<AT>((float*)out, (float*)out_t, (AT*)out2, (AT*)out2_t, A, A_t, B, B_t, v, v_t, ga, n, hw, c, st); break;
+      case 7: launch_avgpool2<AT>((AT*)out, A, n, h, w, c, 2, st); break;
+      default: launch_avgpool2_bwd<AT>((AT*)out, A, n, h, w, c, 2, st); break;
+    }
+  };
+  if (dtype == MDD_DTYPE_F32) run((float*)nullptr); else run((bf16*)nullptr);
+  POST_LAUNCH("op_pool_se");
+  return 0;
+}
+
 int mdd_retrieval_ranks(const float* img_feat, const float* txt_feat, const int* img2txt_off,
                         const int* img2txt_idx, const int* txt2img, int n_img, int n_txt, int dim,
                         float scale, float* scores_ws, float* norm_ws, int* rank_i2t, int* rank_t2i,
