@@ -45,7 +45,7 @@ int mdd_set_error_msg(int code, const char* msg) {
   do { if (!(cond)) return mdd_set_error_msg(2, "mdd: invalid argument: " msg); } while (0)
 #define POST_LAUNCH(what) HIP_CHECK_RET(hipGetLastError())
 // inside Eng<AT> walkers: launch errors + latched stream-ordering / event errors
-#define POST_WALK(what)                                  \
+#define POST_WALK()                                      \
   do {                                                   \
     HIP_CHECK_RET(hipGetLastError());                    \
     if (int rc_ = async_status()) return rc_;            \
@@ -238,8 +238,8 @@ struct Eng : mdd_engine {
   std::vector<ConvL> convs;
   std::vector<Blk> blks;
   int stem[4], fin;
-  int walker = 0;          // 0 NFNet (img_forward / img_backward), 1 NF-ResNet (res_*), 2 NF-RegNet (reg_*)
-  int fpool = 0;           // width of the globally pooled features (= feat unless a classifier follows: NF-ResNet)
+  int walker = 0;          // 0 NFNet (nfnet_forward / nfnet_backward), 1 NF-ResNet (res_*), 2 NF-RegNet (reg_*)
+  int fpool = 0;           // width of the globally pooled features (= feat unless a classifier follows: NF-ResNet, NF-RegNet)
   int ract = 0;            // ConvEpi::act of the residual branches' fused epilogues (0 SiLU, 3 ReLU)
   ConvL stem_col;          // NF-ResNet: the 7x7 stem as a pointwise contraction over its columns (same packed weights)
   std::vector<int> xh, xc;  // stream spatial dim / channels: X[b], b = 0..nb
@@ -267,7 +267,7 @@ struct Eng : mdd_engine {
     AT *VCOL = nullptr, *VPE = nullptr, *VCOLB = nullptr, *VPEB = nullptr;   // patch columns, patch embedding (+ grads)
     AT *CLS = nullptr, *CLSN = nullptr, *CLSNB = nullptr, *CLSB = nullptr, *TMP = nullptr;
     float *hin = nullptr, *hinB = nullptr;     // classifier input / its gradient (fp32): the ViT's normalised class token,
-                                               // NF-ResNet's pooled features
+                                               // the pooled features of NF-ResNet / NF-RegNet
     uint8_t* PIDX = nullptr;                   // NF-ResNet stem max pool: window index of every pooled element
     AT* COL = nullptr;                         // NF-ResNet stem columns [n*ho*wo, 49*8] (see stem_col)
     std::vector<VitActs> vb;
@@ -395,8 +395,9 @@ struct Eng : mdd_engine {
         lpd.push_back(d);
       }
     } else {
-    // the two walkers: NFNet (deep_quad stem, squeeze-excite, conv2b, final conv) and the plain residual one of
-    // NF-ResNet (7x7_pool stem, none of those three); other mixes of the switches have no walker
+    // the three walkers: NFNet (deep_quad stem, squeeze-excite behind conv3, conv2b, final conv), the plain residual one
+    // of NF-ResNet (7x7_pool stem, none of those three, classifier) and NF-RegNet (one-conv stem, squeeze-excite on the
+    // mid channels, final conv, classifier); other mixes of the switches have no walker
     const bool nfnet_like = !nf.stem_pool && nf.se && nf.conv2b && nf.final_conv && !nf.classes;
     const bool plain_res = nf.stem_pool == 1 && !nf.se && !nf.conv2b && !nf.final_conv;
     const bool reg_like = nf.stem_pool == 2 && nf.reg && nf.se && nf.se_mid && !nf.conv2b && nf.final_conv && nf.classes &&
@@ -552,158 +553,105 @@ struct Eng : mdd_engine {
       plan(&a.AB, M * 4 * D, (p + "AB").c_str(), slot);
     }
     plan(&s.y, n * feat, "y", slot); plan(&s.yB, n * feat, "yB", slot);
-    plan(&s.tx, n * Dt, "tx", slot); plan(&s.tp, n * feat, "tp", slot); plan(&s.tg, n * feat, "tg", slot);
-    plan(&s.tf, n * feat, "tf", slot); plan(&s.tr, n * feat, "tr", slot); plan(&s.ty, n * feat, "ty", slot);
-    plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
-    plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
+    plan_text_head(s, slot);
   }
-  // NF-ResNet (7x7_pool stem, no squeeze-excite / conv2b / final conv): stem conv output + pooled stream + window index,
-  // per block {C1, A1, C2, A2, C3} and their gradients, the pooled features in front of the classifier
-  void plan_set_res(ActSet& s, int slot) {
-    const int nb = (int)blks.size();
+  // the text projection head's activations and their gradients: the tail of every plan
+  void plan_text_head(ActSet& s, int slot) {
     const int64_t n = N;
-    const ConvL& L0 = convs[stem[0]];
-    // the image has no tangent and the tangent passes read the window index and the columns of the primal slot:
-    // the tangent set (slot -1) has no input, columns or index of its own
-    s.X0 = s.COL = nullptr; s.PIDX = nullptr;
-    if (slot >= 0) plan(&s.X0, n * S * S * 8, "IN", slot);
-    const int64_t e0 = n * L0.hout * L0.hout * L0.cout;
-    plan(&s.Cs[0], e0, "stem.C0", slot); plan(&s.CsB[0], e0, "stem.CB0", slot);
-    if (slot >= 0) {
-      plan(&s.PIDX, n * xh[0] * xh[0] * xc[0], nullptr, slot);
-      plan(&s.COL, n * L0.hout * L0.hout * stem_col.cin_pad, nullptr, slot);
-    }
-    plan(&s.X0B, n * S * S * 8, "INB", slot);
-    s.X.resize(nb + 1); s.A.resize(nb + 1); s.XB.resize(nb + 1); s.blk.resize(nb);
-    for (int b = 0; b <= nb; ++b) {
-      int64_t e = n * xh[b] * xh[b] * xc[b];
-      plan(&s.X[b], e, ("X" + std::to_string(b)).c_str(), slot);
-      plan(&s.XB[b], e, ("XB" + std::to_string(b)).c_str(), slot);
-      if (b < nb) plan(&s.A[b], e, ("A" + std::to_string(b)).c_str(), slot); else s.A[b] = nullptr;
-    }
-    for (int b = 0; b < nb; ++b) {
-      const Blk& B = blks[b]; BlockActs& a = s.blk[b];
-      memset(&a, 0, sizeof a);
-      std::string p = "b" + std::to_string(b) + ".";
-      int64_t ein = n * B.hin * B.hin, eout = n * B.hout * B.hout;
-      if (B.ds >= 0 && B.stride == 2) plan(&a.P, eout * B.cin, (p + "P").c_str(), slot);
-      if (B.ds >= 0) plan(&a.SC, eout * B.cout, (p + "SC").c_str(), slot);
-      plan(&a.C1, ein * B.mid, (p + "C1").c_str(), slot);   plan(&a.A1, ein * B.mid, (p + "A1").c_str(), slot);
-      plan(&a.C2, eout * B.mid, (p + "C2").c_str(), slot);  plan(&a.A2, eout * B.mid, (p + "A2").c_str(), slot);
-      plan(&a.C3, eout * B.cout, (p + "C3").c_str(), slot);
-      plan(&a.C3B, eout * B.cout, (p + "C3B").c_str(), slot);
-      plan(&a.A2B, eout * B.mid, (p + "A2B").c_str(), slot);   plan(&a.C2B, eout * B.mid, (p + "C2B").c_str(), slot);
-      plan(&a.A1B, ein * B.mid, (p + "A1B").c_str(), slot);    plan(&a.C1B, ein * B.mid, (p + "C1B").c_str(), slot);
-      plan(&a.AinB, ein * B.cin, (p + "AinB").c_str(), slot);
-    }
-    s.CF = s.CFB = nullptr;
-    if (nf.classes > 0) { plan(&s.hin, n * fpool, "pooled", slot); plan(&s.hinB, n * fpool, "pooledB", slot); }
-    plan(&s.y, n * feat, "y", slot); plan(&s.yB, n * feat, "yB", slot);
-    plan(&s.dwf, packed_total, "dwf", slot);
     plan(&s.tx, n * Dt, "tx", slot); plan(&s.tp, n * feat, "tp", slot); plan(&s.tg, n * feat, "tg", slot);
     plan(&s.tf, n * feat, "tf", slot); plan(&s.tr, n * feat, "tr", slot); plan(&s.ty, n * feat, "ty", slot);
     plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
     plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
   }
-  // NF-RegNet (one-conv stem, squeeze-excite between conv2 and conv3, final conv + classifier): the stem conv's raw
-  // output IS the stream X[0]; per block {C1, A1, C2, A2 = silu(ga*gate*C2), C3}, the gate chain {q, h, gate} and their
-  // gradients; the final conv's output and the pooled features in front of the classifier
-  void plan_set_reg(ActSet& s, int slot) {
+  // NormFreeNet stream: X[b], its gradient and the pre-activated A[b] in front of every block, X[nb] behind the last
+  void plan_stream(ActSet& s, int slot) {
     const int nb = (int)blks.size();
-    const int64_t n = N;
-    s.X0 = nullptr;
-    if (slot >= 0) plan(&s.X0, n * S * S * 8, "IN", slot);   // the image has no tangent
-    plan(&s.X0B, n * S * S * 8, "INB", slot);
     s.X.resize(nb + 1); s.A.resize(nb + 1); s.XB.resize(nb + 1); s.blk.resize(nb);
     for (int b = 0; b <= nb; ++b) {
-      int64_t e = n * xh[b] * xh[b] * xc[b];
+      int64_t e = (int64_t)N * xh[b] * xh[b] * xc[b];
       plan(&s.X[b], e, ("X" + std::to_string(b)).c_str(), slot);
       plan(&s.XB[b], e, ("XB" + std::to_string(b)).c_str(), slot);
       if (b < nb) plan(&s.A[b], e, ("A" + std::to_string(b)).c_str(), slot); else s.A[b] = nullptr;
     }
-    for (int b = 0; b < nb; ++b) {
-      const Blk& B = blks[b]; BlockActs& a = s.blk[b];
-      memset(&a, 0, sizeof a);
-      std::string p = "b" + std::to_string(b) + ".";
-      int64_t ein = n * B.hin * B.hin, eout = n * B.hout * B.hout;
-      if (B.ds >= 0 && B.stride == 2) plan(&a.P, eout * B.cin, (p + "P").c_str(), slot);
-      if (B.ds >= 0) plan(&a.SC, eout * B.cout, (p + "SC").c_str(), slot);
-      plan(&a.C1, ein * B.mid, (p + "C1").c_str(), slot);   plan(&a.A1, ein * B.mid, (p + "A1").c_str(), slot);
-      plan(&a.C2, eout * B.mid, (p + "C2").c_str(), slot);  plan(&a.A2, eout * B.mid, (p + "A2").c_str(), slot);
-      plan(&a.C3, eout * B.cout, (p + "C3").c_str(), slot);
-      plan(&a.q, n * B.mid, (p + "q").c_str(), slot);       plan(&a.qB, n * B.mid, (p + "qB").c_str(), slot);
-      plan(&a.h, n * B.se.rd, (p + "h").c_str(), slot);     plan(&a.hB, n * B.se.rd, (p + "hB").c_str(), slot);
-      plan(&a.gate, n * B.mid, (p + "gate").c_str(), slot); plan(&a.zB, n * B.mid, (p + "zB").c_str(), slot);
-      plan(&a.C3B, eout * B.cout, (p + "C3B").c_str(), slot);
-      plan(&a.A2B, eout * B.mid, (p + "A2B").c_str(), slot);   plan(&a.C2B, eout * B.mid, (p + "C2B").c_str(), slot);
-      plan(&a.A1B, ein * B.mid, (p + "A1B").c_str(), slot);    plan(&a.C1B, ein * B.mid, (p + "C1B").c_str(), slot);
-      plan(&a.AinB, ein * B.cin, (p + "AinB").c_str(), slot);
-    }
-    int64_t ef = n * xh[nb] * xh[nb] * fpool;
-    plan(&s.CF, ef, "CF", slot); plan(&s.CFB, ef, "CFB", slot);
-    plan(&s.hin, n * fpool, "pooled", slot); plan(&s.hinB, n * fpool, "pooledB", slot);
-    plan(&s.y, n * feat, "y", slot); plan(&s.yB, n * feat, "yB", slot);
-    plan(&s.dwf, packed_total, "dwf", slot);
-    plan(&s.tx, n * Dt, "tx", slot); plan(&s.tp, n * feat, "tp", slot); plan(&s.tg, n * feat, "tg", slot);
-    plan(&s.tf, n * feat, "tf", slot); plan(&s.tr, n * feat, "tr", slot); plan(&s.ty, n * feat, "ty", slot);
-    plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
-    plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
   }
-  void plan_set(ActSet& s, int slot) {
-    if (is_vit) { plan_set_vit(s, slot); return; }
-    if (walker == 1) { plan_set_res(s, slot); return; }
-    if (walker == 2) { plan_set_reg(s, slot); return; }
-    int nb = (int)blks.size();
-    auto nm = [&](const std::string& n) { return n; };
-    int64_t n = N;
-    plan(&s.X0, n * S * S * 8, "IN", slot);
-    for (int i = 0; i < 3; ++i) {
-      const ConvL& L = convs[stem[i]];
-      int64_t e = n * L.hout * L.hout * L.cout;
-      plan(&s.Cs[i], e, ("stem.C" + std::to_string(i)).c_str(), slot);
-      plan(&s.As[i], e, ("stem.A" + std::to_string(i)).c_str(), slot);
-      plan(&s.AsB[i], e, ("stem.AB" + std::to_string(i)).c_str(), slot);
-      plan(&s.CsB[i], e, ("stem.CB" + std::to_string(i)).c_str(), slot);
-    }
-    plan(&s.X0B, n * S * S * 8, "INB", slot);
-    s.X.resize(nb + 1); s.A.resize(nb + 1); s.XB.resize(nb + 1); s.blk.resize(nb);
-    for (int b = 0; b <= nb; ++b) {
-      int64_t e = n * xh[b] * xh[b] * xc[b];
-      plan(&s.X[b], e, ("X" + std::to_string(b)).c_str(), slot);
-      plan(&s.XB[b], e, ("XB" + std::to_string(b)).c_str(), slot);
-      if (b < nb) plan(&s.A[b], e, ("A" + std::to_string(b)).c_str(), slot); else s.A[b] = nullptr;
-    }
-    for (int b = 0; b < nb; ++b) {
-      const Blk& B = blks[b]; BlockActs& a = s.blk[b];
-      std::string p = "b" + std::to_string(b) + ".";
-      int64_t ein = n * B.hin * B.hin, eout = n * B.hout * B.hout;
-      a.P = nullptr; a.SC = nullptr;
-      if (B.ds >= 0 && B.stride == 2) plan(&a.P, eout * B.cin, (p + "P").c_str(), slot);
-      if (B.ds >= 0) plan(&a.SC, eout * B.cout, (p + "SC").c_str(), slot);
-      plan(&a.C1, ein * B.mid, (p + "C1").c_str(), slot);   plan(&a.A1, ein * B.mid, (p + "A1").c_str(), slot);
-      plan(&a.C2, eout * B.mid, (p + "C2").c_str(), slot);  plan(&a.A2, eout * B.mid, (p + "A2").c_str(), slot);
-      plan(&a.C2b, eout * B.mid, (p + "C2b").c_str(), slot); plan(&a.A2b, eout * B.mid, (p + "A2b").c_str(), slot);
-      plan(&a.C3, eout * B.cout, (p + "C3").c_str(), slot);
+  // One residual block: the frame every topology has {P, SC, C1, A1, C2, A2, C3 | C3B, A2B, C2B, A1B, C1B, AinB}, with
+  // what the topology adds at the place it is produced: NFNet's conv2b pair and its gate chain behind conv3
+  // {q, p, h, gate}, NF-RegNet's gate chain on the mid channels {q, h, gate} (A2 = silu(ga*gate*C2) there)
+  void plan_block(ActSet& s, int b, int slot) {
+    const Blk& B = blks[b]; BlockActs& a = s.blk[b];
+    memset(&a, 0, sizeof a);
+    const std::string p = "b" + std::to_string(b) + ".";
+    const int64_t n = N, ein = n * B.hin * B.hin, eout = n * B.hout * B.hout;
+    const bool se_last = nf.se && !nf.se_mid, se_mid = nf.se && nf.se_mid;
+    if (B.ds >= 0 && B.stride == 2) plan(&a.P, eout * B.cin, (p + "P").c_str(), slot);
+    if (B.ds >= 0) plan(&a.SC, eout * B.cout, (p + "SC").c_str(), slot);
+    plan(&a.C1, ein * B.mid, (p + "C1").c_str(), slot);   plan(&a.A1, ein * B.mid, (p + "A1").c_str(), slot);
+    plan(&a.C2, eout * B.mid, (p + "C2").c_str(), slot);  plan(&a.A2, eout * B.mid, (p + "A2").c_str(), slot);
+    if (nf.conv2b) { plan(&a.C2b, eout * B.mid, (p + "C2b").c_str(), slot); plan(&a.A2b, eout * B.mid, (p + "A2b").c_str(), slot); }
+    plan(&a.C3, eout * B.cout, (p + "C3").c_str(), slot);
+    if (se_last) {
       plan(&a.q, n * B.mid, (p + "q").c_str(), slot); plan(&a.qB, n * B.mid, (p + "qB").c_str(), slot);
       plan(&a.p, n * B.se.c, (p + "p").c_str(), slot); plan(&a.h, n * B.se.rd, (p + "h").c_str(), slot);
       plan(&a.gate, n * B.se.c, (p + "gate").c_str(), slot);
-      plan(&a.C3B, eout * B.cout, (p + "C3B").c_str(), slot);
-      plan(&a.A2bB, eout * B.mid, (p + "A2bB").c_str(), slot); plan(&a.C2bB, eout * B.mid, (p + "C2bB").c_str(), slot);
-      plan(&a.A2B, eout * B.mid, (p + "A2B").c_str(), slot);   plan(&a.C2B, eout * B.mid, (p + "C2B").c_str(), slot);
-      plan(&a.A1B, ein * B.mid, (p + "A1B").c_str(), slot);    plan(&a.C1B, ein * B.mid, (p + "C1B").c_str(), slot);
-      plan(&a.AinB, ein * B.cin, (p + "AinB").c_str(), slot);
+    }
+    if (se_mid) {
+      plan(&a.q, n * B.mid, (p + "q").c_str(), slot);       plan(&a.qB, n * B.mid, (p + "qB").c_str(), slot);
+      plan(&a.h, n * B.se.rd, (p + "h").c_str(), slot);     plan(&a.hB, n * B.se.rd, (p + "hB").c_str(), slot);
+      plan(&a.gate, n * B.mid, (p + "gate").c_str(), slot); plan(&a.zB, n * B.mid, (p + "zB").c_str(), slot);
+    }
+    plan(&a.C3B, eout * B.cout, (p + "C3B").c_str(), slot);
+    if (nf.conv2b) { plan(&a.A2bB, eout * B.mid, (p + "A2bB").c_str(), slot); plan(&a.C2bB, eout * B.mid, (p + "C2bB").c_str(), slot); }
+    plan(&a.A2B, eout * B.mid, (p + "A2B").c_str(), slot);   plan(&a.C2B, eout * B.mid, (p + "C2B").c_str(), slot);
+    plan(&a.A1B, ein * B.mid, (p + "A1B").c_str(), slot);    plan(&a.C1B, ein * B.mid, (p + "C1B").c_str(), slot);
+    plan(&a.AinB, ein * B.cin, (p + "AinB").c_str(), slot);
+    if (se_last) {
       plan(&a.zB, n * B.se.c, (p + "zB").c_str(), slot);
       plan(&a.hB, n * B.se.rd, (p + "hB").c_str(), slot);      plan(&a.pB, n * B.se.c, (p + "pB").c_str(), slot);
     }
-    int64_t ef = n * xh[nb] * xh[nb] * feat;
-    plan(&s.CF, ef, "CF", slot); plan(&s.CFB, ef, "CFB", slot);
+  }
+  // The three NormFreeNet topologies: input and stem (deep_quad: three stashed convs, the fourth one's output is the
+  // stream; 7x7_pool: conv output, window index and columns; 3x3: the conv's output IS the stream), stream, blocks,
+  // final conv, pooled features in front of a classifier, features, packed weight gradient, text head
+  void plan_set_nf(ActSet& s, int slot) {
+    const int nb = (int)blks.size();
+    const int64_t n = N;
+    // the image has no tangent and the tangent passes read the window index and the columns of the primal slot: the
+    // tangent set (slot -1) has no input, columns or index of its own (the deep_quad plan keeps its unused input)
+    s.X0 = s.COL = nullptr; s.PIDX = nullptr;
+    if (slot >= 0 || nf.stem_pool == 0) plan(&s.X0, n * S * S * 8, "IN", slot);
+    if (nf.stem_pool == 0) {
+      for (int i = 0; i < 3; ++i) {
+        const ConvL& L = convs[stem[i]];
+        int64_t e = n * L.hout * L.hout * L.cout;
+        plan(&s.Cs[i], e, ("stem.C" + std::to_string(i)).c_str(), slot);
+        plan(&s.As[i], e, ("stem.A" + std::to_string(i)).c_str(), slot);
+        plan(&s.AsB[i], e, ("stem.AB" + std::to_string(i)).c_str(), slot);
+        plan(&s.CsB[i], e, ("stem.CB" + std::to_string(i)).c_str(), slot);
+      }
+    } else if (nf.stem_pool == 1) {
+      const ConvL& L0 = convs[stem[0]];
+      const int64_t e0 = n * L0.hout * L0.hout * L0.cout;
+      plan(&s.Cs[0], e0, "stem.C0", slot); plan(&s.CsB[0], e0, "stem.CB0", slot);
+      if (slot >= 0) {
+        plan(&s.PIDX, n * xh[0] * xh[0] * xc[0], nullptr, slot);
+        plan(&s.COL, n * L0.hout * L0.hout * stem_col.cin_pad, nullptr, slot);
+      }
+    }
+    plan(&s.X0B, n * S * S * 8, "INB", slot);
+    plan_stream(s, slot);
+    for (int b = 0; b < nb; ++b) plan_block(s, b, slot);
+    s.CF = s.CFB = nullptr;
+    if (nf.final_conv) {
+      int64_t ef = n * xh[nb] * xh[nb] * fpool;
+      plan(&s.CF, ef, "CF", slot); plan(&s.CFB, ef, "CFB", slot);
+    }
+    if (nf.classes > 0) { plan(&s.hin, n * fpool, "pooled", slot); plan(&s.hinB, n * fpool, "pooledB", slot); }
     plan(&s.y, n * feat, "y", slot); plan(&s.yB, n * feat, "yB", slot);
     plan(&s.dwf, packed_total, "dwf", slot);
-    plan(&s.tx, n * Dt, "tx", slot); plan(&s.tp, n * feat, "tp", slot); plan(&s.tg, n * feat, "tg", slot);
-    plan(&s.tf, n * feat, "tf", slot); plan(&s.tr, n * feat, "tr", slot); plan(&s.ty, n * feat, "ty", slot);
-    plan(&s.tyB, n * feat, "tyB", slot); plan(&s.trB, n * feat, "trB", slot); plan(&s.tfB, n * feat, "tfB", slot);
-    plan(&s.tgB, n * feat, "tgB", slot); plan(&s.tpB, n * feat, "tpB", slot); plan(&s.txB, n * Dt, "txB", slot);
-    (void)nm;
+    plan_text_head(s, slot);
+  }
+  void plan_set(ActSet& s, int slot) {
+    if (is_vit) plan_set_vit(s, slot); else plan_set_nf(s, slot);
   }
 
   void plan_workspace() {
@@ -833,7 +781,7 @@ struct Eng : mdd_engine {
   size_t evi = 0;
   // The stream-ordering helpers below are called from inside the walkers (void lambdas, queued
   // closures); the first failing HIP call is latched here and turned into the pass's return code by
-  // ASYNC_CHECK at the end of every walker -- a failed event record / stream wait would otherwise
+  // POST_WALK at the end of every walker -- a failed event record / stream wait would otherwise
   // silently drop a dependency between the main and the side stream.
   hipError_t aerr = hipSuccess;
   const char* aerr_what = "";
@@ -1035,9 +983,9 @@ struct Eng : mdd_engine {
     else gemm(L, g, dy_t, wt + L.off_p, dy, wt_t + L.off_p, e, st);
   }
   ConvEpi epi_act(bool T, AT* raw, AT* act, AT* act_t, const AT* c, const AT* c_t, float beta,
-                  const AT* add1, const AT* add2) {
+                  const AT* add1, const AT* add2, int act_kind = 0) {
     ConvEpi e; memset(&e, 0, sizeof e);
-    e.beta = beta; e.add1 = add1; e.add2 = add2; e.c = c;
+    e.beta = beta; e.add1 = add1; e.add2 = add2; e.c = c; e.act = act_kind;
     if (!T) { e.mode = EPI_BWD; e.out_raw = raw; e.out_act = act; }
     else { e.mode = EPI_BWD_T; e.out_raw = nullptr; e.out_act = act_t; e.c_t = c_t; e.abar = raw; }
     return e;
@@ -1045,6 +993,14 @@ struct Eng : mdd_engine {
   ConvEpi epi_lin(AT* raw, const AT* add1) {
     ConvEpi e; memset(&e, 0, sizeof e);
     e.mode = EPI_BWD_LIN; e.out_raw = raw; e.add1 = add1; e.beta = 1.f; return e;
+  }
+  // a tangent argument of a launcher: null in a primal pass (the launchers pick the primal kernel by it)
+  static const float* tp(bool T, const float* q) { return T ? q : nullptr; }
+  // packed weights of every contraction (and their tangents): weight standardisation, or the ViT's cast / transpose
+  void pack_weights(bool T, const float* th, const float* th_t, hipStream_t st) {
+    if (is_vit) launch_lin_pack_all<AT>(d_lpd, (int)lpd.size(), lpd_tiles, th, T ? th_t : nullptr, wf, wt, wf_t, wt_t, st);
+    else launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt, wf_t,
+                               wt_t, st);
   }
 
   // ================================================================== ViT image encoder (BASELINE configs[4])
@@ -1056,9 +1012,6 @@ struct Eng : mdd_engine {
   // the attention contractions follow the engine's precision mode: exact FMA (f32), split-bf16 MFMA (bf16x2), bf16 MFMA
   int bdt() const { return sizeof(AT) == 4 ? (prec == 1 ? MDD_DTYPE_BF16X2 : MDD_DTYPE_F32) : MDD_DTYPE_BF16; }
   std::vector<LinPackDesc> lpd; LinPackDesc* d_lpd = nullptr; int64_t o_lpd = 0; int lpd_tiles = 0;
-  void vit_pack(const float* th, const float* th_t, hipStream_t st) {
-    launch_lin_pack_all<AT>(d_lpd, (int)lpd.size(), lpd_tiles, th, th_t, wf, wt, wf_t, wt_t, st);
-  }
   // the weight gradient of a linear goes to gout + off_w: conv_bwd_w adds the layer's PACKED offset to its base
   void lin_bwd_w(bool T, const ConvL& L, const AT* dy, const AT* dy_t, const AT* x, const AT* x_t, float* gout,
                  hipStream_t st) {
@@ -1095,12 +1048,11 @@ struct Eng : mdd_engine {
     const int64_t rows = (int64_t)N * vit.heads * Tk;
     const float scale = 1.f / std::sqrt((float)(D / vit.heads));
     const AttnDesc ad = attn_desc();
-    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
-    vit_pack(th, T ? th_t : nullptr, st);
+    pack_weights(T, th, th_t, st);
     if (!T) launch_patchify<AT>(P.VCOL, image, idx, N, S, vit.patch, st);
     conv_fwd(T, convs[pe_conv], P.VCOL, nullptr, P.VPE, Q.VPE, nullptr, nullptr, 1.f, th, th_t, st);
     launch_vit_embed<AT>(P.X[0], T ? Q.X[0] : nullptr, P.VPE, T ? Q.VPE : nullptr, th + off_cls,
-                         tp(th_t + off_cls), th + off_pos, tp(th_t + off_pos), N, Tk, D, st);
+                         tp(T, th_t + off_cls), th + off_pos, tp(T, th_t + off_pos), N, Tk, D, st);
     for (int l = 0; l < vit.depth; ++l) {
       const VitBlkL& B = vblk[l]; VitActs& pa = P.vb[l]; VitActs& qa = Q.vb[l];
       const AT *x = P.X[l], *x_t = T ? Q.X[l] : nullptr;
@@ -1108,11 +1060,11 @@ struct Eng : mdd_engine {
         // x_l = x2_{l-1} + fc2 output (still in TMP) is formed by the kernel that normalises it
         VitActs& pp = P.vb[l - 1]; VitActs& qp = Q.vb[l - 1];
         VIT_RC(mdd_op_add_layernorm(VDT, M, D, vit.eps, pp.X2, T ? qp.X2 : nullptr, P.TMP, T ? Q.TMP : nullptr, P.X[l],
-                                    T ? Q.X[l] : nullptr, th + B.ln1_w, tp(th_t + B.ln1_w), th + B.ln1_b, tp(th_t + B.ln1_b),
+                                    T ? Q.X[l] : nullptr, th + B.ln1_w, tp(T, th_t + B.ln1_w), th + B.ln1_b, tp(T, th_t + B.ln1_b),
                                     pa.N1, T ? qa.N1 : nullptr, st));
       } else {
-        VIT_RC(mdd_op_layernorm(VDT, M, D, vit.eps, x, x_t, th + B.ln1_w, tp(th_t + B.ln1_w), th + B.ln1_b,
-                                tp(th_t + B.ln1_b), pa.N1, T ? qa.N1 : nullptr, st));
+        VIT_RC(mdd_op_layernorm(VDT, M, D, vit.eps, x, x_t, th + B.ln1_w, tp(T, th_t + B.ln1_w), th + B.ln1_b,
+                                tp(T, th_t + B.ln1_b), pa.N1, T ? qa.N1 : nullptr, st));
       }
       conv_fwd(T, convs[B.qkv], pa.N1, qa.N1, pa.QKV, qa.QKV, nullptr, nullptr, 1.f, th, th_t, st);
       // attention: scores -> probabilities (in place) -> weighted values.  Tangent of the softmax from the stashed
@@ -1138,7 +1090,7 @@ struct Eng : mdd_engine {
       conv_fwd(T, convs[B.proj], pa.O, qa.O, P.TMP, Q.TMP, nullptr, nullptr, 1.f, th, th_t, st);
       // a residual sum is formed by the LayerNorm kernel that reads it
       VIT_RC(mdd_op_add_layernorm(VDT, M, D, vit.eps, x, x_t, P.TMP, T ? Q.TMP : nullptr, pa.X2, T ? qa.X2 : nullptr,
-                                  th + B.ln2_w, tp(th_t + B.ln2_w), th + B.ln2_b, tp(th_t + B.ln2_b), pa.N2,
+                                  th + B.ln2_w, tp(T, th_t + B.ln2_w), th + B.ln2_b, tp(T, th_t + B.ln2_b), pa.N2,
                                   T ? qa.N2 : nullptr, st));
       // fc1 with the exact GELU in its epilogue (C and A = gelu(C) written by the contraction; tangent: C_t and
       // A_t = gelu'(C) C_t) wherever the GELU instance of the kernel exists for this width
@@ -1155,23 +1107,17 @@ struct Eng : mdd_engine {
     }
     // feature = LayerNorm(x_L)[:, 0]: normalise the class rows only
     launch_cls_gather<AT>(T ? Q.CLS : P.CLS, T ? Q.X[vit.depth] : P.X[vit.depth], N, Tk, D, st);
-    VIT_RC(mdd_op_layernorm(VDT, N, D, vit.eps, P.CLS, T ? Q.CLS : nullptr, th + off_nw, tp(th_t + off_nw),
-                            th + off_nb, tp(th_t + off_nb), P.CLSN, T ? Q.CLSN : nullptr, st));
+    VIT_RC(mdd_op_layernorm(VDT, N, D, vit.eps, P.CLS, T ? Q.CLS : nullptr, th + off_nw, tp(T, th_t + off_nw),
+                            th + off_nb, tp(T, th_t + off_nb), P.CLSN, T ? Q.CLSN : nullptr, st));
     if (vit.head > 0) {
       // classifier head on the normalised class token (timm default; reference networks.py:668): small-batch fp32 linear
       launch_act_to_f32<AT>(T ? Q.hin : P.hin, T ? Q.CLSN : P.CLSN, (int64_t)N * D, st);
-      launch_linear_fwd(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_hw, tp(th_t + off_hw),
-                        th + off_hb, tp(th_t + off_hb), N, D, vit.head, 0, lin_main, st);
-      if (!T && feat_out && feat_out != P.y)
-        HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
-    } else if (!T) {
-      launch_act_to_f32<AT>(P.y, P.CLSN, (int64_t)N * D, st);
-      if (feat_out && feat_out != P.y)
-        HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+      classifier_fwd(T, P, Q, D, vit.head, th, th_t, feat_out, st);
     } else {
-      launch_act_to_f32<AT>(feat_out, Q.CLSN, (int64_t)N * D, st);
+      launch_act_to_f32<AT>(T ? feat_out : P.y, T ? Q.CLSN : P.CLSN, (int64_t)N * D, st);
     }
-    POST_WALK("vit_forward");
+    VIT_RC(copy_features(T, P, feat_out, st));
+    POST_WALK();
     return 0;
   }
   int vit_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in,
@@ -1183,24 +1129,17 @@ struct Eng : mdd_engine {
     const int64_t rows = (int64_t)N * vit.heads * Tk;
     const float scale = 1.f / std::sqrt((float)(D / vit.heads));
     const AttnDesc ad = attn_desc();
-    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
     // gradient slices: a primal call fills gout with d/d theta, a tangent call with its tangent
     auto gp = [&](int64_t off) { return T ? (float*)nullptr : gout + off; };
     auto gt = [&](int64_t off) { return T ? gout + off : (float*)nullptr; };
-    if (repack) vit_pack(th, T ? th_t : nullptr, st);
-    HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
-    if (!T && ybar_in != O.yB)
-      HIP_CHECK_RET(hipMemcpyAsync(O.yB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    VIT_RC(walk_bwd_begin(T, repack, O, ybar_in, gout, th, th_t, st));
     if (vit.head > 0) {
-      launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N, D,
-                          vit.head, lin_main, st);
-      launch_linear_dgrad(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_hw, tp(th_t + off_hw),
-                          nullptr, N, D, vit.head, lin_main, st);
+      classifier_bwd(T, P, Q, O, D, vit.head, ybar_t_in, gout, th, th_t, st);
       launch_f32_to_act<AT>(T ? Q.CLSNB : O.CLSNB, T ? Q.hinB : O.hinB, (int64_t)N * D, st);
     } else
     launch_f32_to_act<AT>(T ? Q.CLSNB : O.CLSNB, T ? ybar_t_in : O.yB, (int64_t)N * D, st);
     VIT_RC(mdd_op_layernorm_bwd(VDT, N, D, vit.eps, P.CLS, T ? Q.CLS : nullptr, O.CLSNB, T ? Q.CLSNB : nullptr,
-                                th + off_nw, tp(th_t + off_nw), nullptr, nullptr, T ? nullptr : O.CLSB,
+                                th + off_nw, tp(T, th_t + off_nw), nullptr, nullptr, T ? nullptr : O.CLSB,
                                 T ? Q.CLSB : nullptr, gp(off_nw), gt(off_nw), gp(off_nb), gt(off_nb), st));
     launch_cls_scatter<AT>(T ? Q.XB[L_] : O.XB[L_], T ? Q.CLSB : O.CLSB, N, Tk, D, st);
     for (int l = L_ - 1; l >= 0; --l) {
@@ -1211,9 +1150,7 @@ struct Eng : mdd_engine {
       if (conv_gemm_supports_gelu(gdgrad(convs[B.fc2]))) {
         // fc2's data gradient with the GELU chain rule in its epilogue: raw AB (stashed: the tangent pass needs it)
         // and CB = gelu'(C) AB; tangent: CB_t = (gelu'(Dual(C, C_t)) Dual(AB, AB_t)).t from the stashed C, C_t, AB
-        ConvEpi eg = epi_act(T, oa.AB, oa.CB, qa.CB, pa.C, qa.C, 1.f, nullptr, nullptr);
-        eg.act = 1;
-        conv_bwd_d(T, convs[B.fc2], xb, xb_t, eg, st);
+        conv_bwd_d(T, convs[B.fc2], xb, xb_t, epi_act(T, oa.AB, oa.CB, qa.CB, pa.C, qa.C, 1.f, nullptr, nullptr, 1), st);
       } else {
         conv_bwd_d(T, convs[B.fc2], xb, xb_t, epi_lin(T ? qa.AB : oa.AB, nullptr), st);
         VIT_RC(mdd_op_gelu_bwd(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, oa.AB, T ? qa.AB : nullptr,
@@ -1222,7 +1159,7 @@ struct Eng : mdd_engine {
       lin_bwd_w(T, convs[B.fc1], oa.CB, qa.CB, pa.N2, qa.N2, gout, st);
       conv_bwd_d(T, convs[B.fc1], oa.CB, qa.CB, epi_lin(T ? qa.N2B : oa.N2B, nullptr), st);
       VIT_RC(mdd_op_layernorm_bwd(VDT, M, D, vit.eps, pa.X2, T ? qa.X2 : nullptr, oa.N2B, T ? qa.N2B : nullptr,
-                                  th + B.ln2_w, tp(th_t + B.ln2_w), xb, T ? xb_t : nullptr, T ? nullptr : oa.X2B,
+                                  th + B.ln2_w, tp(T, th_t + B.ln2_w), xb, T ? xb_t : nullptr, T ? nullptr : oa.X2B,
                                   T ? qa.X2B : nullptr, gp(B.ln2_w), gt(B.ln2_w), gp(B.ln2_b), gt(B.ln2_b), st));
       // attention branch
       lin_bwd_w(T, convs[B.proj], oa.X2B, qa.X2B, pa.O, qa.O, gout, st);
@@ -1268,7 +1205,7 @@ struct Eng : mdd_engine {
       lin_bwd_w(T, convs[B.qkv], oa.QKVB, qa.QKVB, pa.N1, qa.N1, gout, st);
       conv_bwd_d(T, convs[B.qkv], oa.QKVB, qa.QKVB, epi_lin(T ? qa.N1B : oa.N1B, nullptr), st);
       VIT_RC(mdd_op_layernorm_bwd(VDT, M, D, vit.eps, P.X[l], T ? Q.X[l] : nullptr, oa.N1B, T ? qa.N1B : nullptr,
-                                  th + B.ln1_w, tp(th_t + B.ln1_w), oa.X2B, T ? qa.X2B : nullptr,
+                                  th + B.ln1_w, tp(T, th_t + B.ln1_w), oa.X2B, T ? qa.X2B : nullptr,
                                   T ? nullptr : O.XB[l], T ? Q.XB[l] : nullptr, gp(B.ln1_w), gt(B.ln1_w),
                                   gp(B.ln1_b), gt(B.ln1_b), st));
       flush_w(st);
@@ -1283,10 +1220,173 @@ struct Eng : mdd_engine {
     }
     flush_w(st, MAIN_TAIL);
     join(st);
-    POST_WALK("vit_backward");
+    POST_WALK();
     return 0;
   }
 #undef VIT_RC
+
+  // ================================================================== NormFreeNet image encoders: the shared block frame
+  // The three walkers below (NFNet, NF-ResNet, NF-RegNet) are scripts of their own topology -- stem, what sits between
+  // conv1 and conv3, where the squeeze-excite gate sits -- over the stages every one of them has, which live here once.
+  // Roles of the activation sets: P holds the primal stash of the slot, Q = tn the tangents, O the primal backward
+  // signals (tn when they are not stashed).  Launchers pick the primal kernel by a null tangent pointer, so the
+  // stages pass `T ? q : nullptr` exactly where the walkers did.
+
+  // start of a forward pass: standardised weights (and their tangents), the NHWC image batch of a primal pass
+  void walk_fwd_begin(bool T, ActSet& P, const float* th, const float* th_t, const float* image, const int64_t* idx,
+                      hipStream_t st) {
+    pack_weights(T, th, th_t, st);
+    if (!T) launch_img_gather_nhwc<AT>(P.X0, image, idx, N, 3, S, S, 8, st);
+  }
+  // The shortcut of a downsampling block (avg-pool 2 when it strides, 1x1 conv) only meets the residual branch where
+  // the block's output is formed: it runs on the side stream, which is idle during forward passes.  Returns whether
+  // the caller has to join(st) before it reads sc / sc_t (left alone for an identity shortcut).
+  bool shortcut_fwd(bool T, const Blk& B, BlockActs& pa, BlockActs& qa, const AT* a, const AT* a_t, const float* th,
+                    const float* th_t, hipStream_t st, const AT*& sc, const AT*& sc_t) {
+    if (B.ds < 0) return false;
+    hipStream_t ss = st;
+    bool forked = false;
+    if (use_side) { fork(st); ss = side; forked = true; }
+    const AT *din = a, *din_t = a_t;
+    if (B.stride == 2) {
+      launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
+      din = pa.P; din_t = qa.P;
+    }
+    conv_fwd(T, convs[B.ds], din, din_t, pa.SC, qa.SC, nullptr, nullptr, 1.f, th, th_t, ss);
+    sc = pa.SC; sc_t = qa.SC;
+    return forked;
+  }
+  // the two linears of a squeeze-excite gate: h = relu(fc1(in)), gate = sigmoid(fc2(h))
+  void se_mlp_fwd(bool T, const Blk& B, BlockActs& pa, BlockActs& qa, const float* in, const float* in_t,
+                  const float* th, const float* th_t, hipStream_t gs) {
+    const int c = B.se.c, rd = B.se.rd;
+    launch_linear_fwd(pa.h, T ? qa.h : nullptr, in, T ? in_t : nullptr, th + B.se.off_w1, tp(T, th_t + B.se.off_w1),
+                      th + B.se.off_b1, tp(T, th_t + B.se.off_b1), N, c, rd, 1, lin_main, gs);
+    launch_linear_fwd(pa.gate, T ? qa.gate : nullptr, pa.h, T ? qa.h : nullptr, th + B.se.off_w2,
+                      tp(T, th_t + B.se.off_w2), th + B.se.off_b2, tp(T, th_t + B.se.off_b2), N, rd, c, 2, lin_main, gs);
+  }
+  // ... and their data gradients: hB from the gate's pre-sigmoid gradient zB, then dx = fc1^T hB
+  void se_mlp_bwd(bool T, const Blk& B, BlockActs& oa, BlockActs& pa, BlockActs& qa, float* dx, float* dx_t,
+                  const float* th, const float* th_t, hipStream_t st) {
+    const int c = B.se.c, rd = B.se.rd;
+    launch_linear_dgrad(oa.hB, T ? qa.hB : nullptr, oa.zB, T ? qa.zB : nullptr, th + B.se.off_w2,
+                        tp(T, th_t + B.se.off_w2), pa.h, N, rd, c, lin_main, st);
+    launch_linear_dgrad(dx, T ? dx_t : nullptr, oa.hB, T ? qa.hB : nullptr, th + B.se.off_w1,
+                        tp(T, th_t + B.se.off_w1), nullptr, N, c, rd, lin_main, st);
+  }
+  // ... and their weight gradients (in / in_t: fc1's input), queued for the next flush_w.  The closure captures by
+  // value and asks for the split-K scratch of the stream it runs on when it runs.
+  void queue_se_wgrads(bool T, const Blk& B, BlockActs& oa, BlockActs& pa, BlockActs& qa, const float* in,
+                       const float* in_t, float* gout) {
+    const float *zB = oa.zB, *zB_t = T ? qa.zB : nullptr, *hh = pa.h, *hh_t = T ? qa.h : nullptr;
+    const float *hB = oa.hB, *hB_t = T ? qa.hB : nullptr, *ii = in, *ii_t = T ? in_t : nullptr;
+    float *gw2 = gout + B.se.off_w2, *gb2 = gout + B.se.off_b2, *gw1 = gout + B.se.off_w1, *gb1 = gout + B.se.off_b1;
+    const int n_ = N, c = B.se.c, rd = B.se.rd;
+    wq.push_back([=](hipStream_t ws_) {
+      launch_linear_wgrad(gw2, gb2, zB, zB_t, hh, hh_t, n_, rd, c, wlin(), ws_);
+      launch_linear_wgrad(gw1, gb1, hB, hB_t, ii, ii_t, n_, c, rd, wlin(), ws_);
+    });
+  }
+  void final_conv_fwd(bool T, ActSet& P, ActSet& Q, const float* th, const float* th_t, hipStream_t st) {
+    const int nb = (int)blks.size();
+    conv_fwd(T, convs[fin], P.X[nb], Q.X[nb], P.CF, Q.CF, nullptr, nullptr, 1.f, th, th_t, st);
+  }
+  void final_conv_bwd(bool T, ActSet& P, ActSet& Q, ActSet& O, float* dw, float* dw_t, float* gout, hipStream_t st) {
+    const int nb = (int)blks.size();
+    conv_bwd_w(T, convs[fin], O.CFB, Q.CFB, P.X[nb], Q.X[nb], dw, dw_t, gout, st);
+    conv_bwd_d(T, convs[fin], O.CFB, Q.CFB, epi_lin(T ? Q.XB[nb] : O.XB[nb], nullptr), st);
+  }
+  // classifier Linear(in, out) on the fp32 features hin (small-batch linear): the features are its logits
+  void classifier_fwd(bool T, ActSet& P, ActSet& Q, int in, int out, const float* th, const float* th_t, float* feat_out,
+                      hipStream_t st) {
+    launch_linear_fwd(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_hw, tp(T, th_t + off_hw),
+                      th + off_hb, tp(T, th_t + off_hb), N, in, out, 0, lin_main, st);
+  }
+  void classifier_bwd(bool T, ActSet& P, ActSet& Q, ActSet& O, int in, int out, const float* ybar_t_in, float* gout,
+                      const float* th, const float* th_t, hipStream_t st) {
+    launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N, in, out,
+                        lin_main, st);
+    launch_linear_dgrad(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_hw, tp(T, th_t + off_hw),
+                        nullptr, N, in, out, lin_main, st);
+  }
+  int copy_features(bool T, ActSet& P, float* feat_out, hipStream_t st) {
+    if (!T && feat_out && feat_out != P.y)
+      HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    return 0;
+  }
+  // head: final activation (SiLU, or ReLU: nf.relu) + global average pool of x (the stream, or the final conv's
+  // output), the classifier where the topology keeps one, the features to feat_out; ends the forward pass
+  int head_fwd(bool T, ActSet& P, ActSet& Q, const AT* x, const AT* x_t, const float* th, const float* th_t,
+               float* feat_out, hipStream_t st) {
+    const int nb = (int)blks.size(), hwf = xh[nb] * xh[nb];
+    if (nf.classes > 0) {
+      launch_final_pool<AT>(P.hin, T ? Q.hin : nullptr, x, T ? x_t : nullptr, N, hwf, fpool, st, nf.relu != 0);
+      classifier_fwd(T, P, Q, fpool, nf.classes, th, th_t, feat_out, st);
+    } else {
+      launch_final_pool<AT>(P.y, T ? feat_out : nullptr, x, T ? x_t : nullptr, N, hwf, fpool, st, nf.relu != 0);
+    }
+    if (int rc = copy_features(T, P, feat_out, st)) return rc;
+    POST_WALK();
+    return 0;
+  }
+  // ... backward: gradient of the pooled tensor x into xB (primal) / xB_t (tangent)
+  void head_bwd(bool T, ActSet& P, ActSet& Q, ActSet& O, const float* ybar_t_in, const AT* x, const AT* x_t, AT* xB,
+                AT* xB_t, float* gout, const float* th, const float* th_t, hipStream_t st) {
+    const int nb = (int)blks.size(), hwf = xh[nb] * xh[nb];
+    const float *g = O.yB, *g_t = ybar_t_in;
+    if (nf.classes > 0) {
+      classifier_bwd(T, P, Q, O, fpool, nf.classes, ybar_t_in, gout, th, th_t, st);
+      g = O.hinB; g_t = Q.hinB;
+    }
+    launch_final_pool_bwd<AT>(xB, T ? xB_t : nullptr, g, T ? g_t : nullptr, x, T ? x_t : nullptr, N, hwf, fpool, st,
+                              nf.relu != 0);
+  }
+  // start of a backward pass: optional repack, zeroed flat gradient, the feature gradient into the set's yB
+  // (no zero-fill of dwf: every conv's two-phase weight gradient overwrites its whole packed slice)
+  int walk_bwd_begin(bool T, bool repack, ActSet& O, const float* ybar_in, float* gout, const float* th,
+                     const float* th_t, hipStream_t st) {
+    if (repack) pack_weights(T, th, th_t, st);
+    HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
+    if (!T && ybar_in != O.yB)
+      HIP_CHECK_RET(hipMemcpyAsync(O.yB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    return 0;
+  }
+  // Input side of a block's backward pass, from conv1's output gradient C1B: conv1's weight gradient, the shortcut
+  // branch (its weight gradient; its data gradient through the scratch dsS, un-pooled into dsF when it strides), then
+  // conv1's data gradient with the pre-activation chain rule and the shortcut in its epilogue:
+  //   XB[b] = beta*act'(X[b])*Abar + (downsample shortcut's gradient | XB[b+1] for an identity shortcut)
+  void block_input_bwd(bool T, int b, ActSet& P, ActSet& Q, ActSet& O, float* dw, float* dw_t, float* gout,
+                       hipStream_t st) {
+    const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b]; BlockActs& oa = O.blk[b];
+    const AT *xb = O.XB[b + 1], *xb_t = Q.XB[b + 1];
+    conv_bwd_w(T, convs[B.c1], oa.C1B, qa.C1B, P.A[b], Q.A[b], dw, dw_t, gout, st);
+    const AT* add1 = nullptr;
+    if (B.ds >= 0) {
+      const AT* dsin = B.stride == 2 ? pa.P : P.A[b];
+      const AT* dsin_t = B.stride == 2 ? qa.P : Q.A[b];
+      conv_bwd_w(T, convs[B.ds], xb, xb_t, dsin, dsin_t, dw, dw_t, gout, st);
+      conv_bwd_d(T, convs[B.ds], xb, xb_t, epi_lin(dsS, nullptr), st);
+      if (B.stride == 2) {
+        launch_avgpool2_bwd<AT>(dsF, dsS, N, B.hin, B.hin, B.cin, 2, st);
+        add1 = dsF;
+      } else {
+        add1 = dsS;
+      }
+    }
+    conv_bwd_d(T, convs[B.c1], oa.C1B, qa.C1B,
+               epi_act(T, oa.AinB, O.XB[b], Q.XB[b], P.X[b], Q.X[b], B.beta, add1,
+                       B.ds >= 0 ? nullptr : (T ? xb_t : xb), ract), st);
+    if (b == 0) flush_w(st);   // the stem's weight gradients do not wait for a next block's flush
+  }
+  // end of a backward pass: what is still queued runs on the main stream (the side stream is the one lagging), then
+  // the weight-standardisation backward turns the packed gradient into the flat one
+  int walk_bwd_end(bool T, float* dw, float* dw_t, float* gout, const float* th, const float* th_t, hipStream_t st) {
+    flush_w(st, MAIN_TAIL);
+    join(st);
+    launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw, T ? dw_t : nullptr, gout, st);
+    POST_WALK();
+    return 0;
+  }
 
   // ================================================================== NF-ResNet image encoder (timm nf_resnet50)
   // stem conv 7x7 / 2 -> max pool 3x3 / 2 -> blocks {a = beta*relu(x); shortcut = x or downsample(a);
@@ -1298,14 +1398,9 @@ struct Eng : mdd_engine {
                   float* feat_out, hipStream_t st) {
     ActSet& P = sets[slot]; ActSet& Q = tn;
     const int nb = (int)blks.size();
-    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
-    launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
-                          wf_t, wt_t, st);
+    walk_fwd_begin(T, P, th, th_t, image, idx, st);
     const ConvL& L0 = convs[stem[0]];
-    if (!T) {
-      launch_img_gather_nhwc<AT>(P.X0, image, idx, N, 3, S, S, 8, st);
-      launch_im2col<AT>(P.COL, P.X0, N, S, S, L0.cin_pad, L0.k, L0.stride, L0.pad, L0.hout, L0.hout, st);
-    }
+    if (!T) launch_im2col<AT>(P.COL, P.X0, N, S, S, L0.cin_pad, L0.k, L0.stride, L0.pad, L0.hout, L0.hout, st);
     conv_fwd(T, stem_col, P.COL, nullptr, P.Cs[0], Q.Cs[0], nullptr, nullptr, 1.f, th, th_t, st);
     if (!T)
       launch_maxpool3s2<AT>(P.X[0], P.PIDX, P.A[0], P.Cs[0], blks[0].beta, N, L0.hout, L0.hout, L0.cout, st);
@@ -1315,19 +1410,7 @@ struct Eng : mdd_engine {
       const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
       const AT *a = P.A[b], *a_t = Q.A[b];
       const AT *sc = P.X[b], *sc_t = Q.X[b];
-      bool sc_forked = false;
-      if (B.ds >= 0) {
-        // the shortcut (avg-pool + 1x1 conv) only meets the residual branch at the residual sum: side stream
-        hipStream_t ss = st;
-        if (use_side) { fork(st); ss = side; sc_forked = true; }
-        const AT *din = a, *din_t = a_t;
-        if (B.stride == 2) {
-          launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
-          din = pa.P; din_t = qa.P;
-        }
-        conv_fwd(T, convs[B.ds], din, din_t, pa.SC, qa.SC, nullptr, nullptr, 1.f, th, th_t, ss);
-        sc = pa.SC; sc_t = qa.SC;
-      }
+      const bool sc_forked = shortcut_fwd(T, B, pa, qa, a, a_t, th, th_t, st, sc, sc_t);
       conv_fwd(T, convs[B.c1], a, a_t, pa.C1, qa.C1, pa.A1, qa.A1, 1.f, th, th_t, st, ract);
       conv_fwd(T, convs[B.c2], pa.A1, qa.A1, pa.C2, qa.C2, pa.A2, qa.A2, 1.f, th, th_t, st, ract);
       conv_fwd(T, convs[B.c3], pa.A2, qa.A2, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
@@ -1337,19 +1420,7 @@ struct Eng : mdd_engine {
                             lastb ? nullptr : P.A[b + 1], (T && !lastb) ? Q.A[b + 1] : nullptr, nf.alpha,
                             lastb ? 1.f : blks[b + 1].beta, (int64_t)N * B.hout * B.hout * B.cout, st);
     }
-    // final_act (ReLU, no beta) + global average pool, then the classifier (small-batch fp32 linear)
-    const int hwf = xh[nb] * xh[nb];
-    if (nf.classes > 0) {
-      launch_final_pool<AT>(P.hin, T ? Q.hin : nullptr, P.X[nb], T ? Q.X[nb] : nullptr, N, hwf, fpool, st, nf.relu != 0);
-      launch_linear_fwd(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_hw, tp(th_t + off_hw),
-                        th + off_hb, tp(th_t + off_hb), N, fpool, nf.classes, 0, lin_main, st);
-    } else {
-      launch_final_pool<AT>(P.y, T ? feat_out : nullptr, P.X[nb], T ? Q.X[nb] : nullptr, N, hwf, feat, st, nf.relu != 0);
-    }
-    if (!T && feat_out && feat_out != P.y)
-      HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
-    POST_WALK("res_forward");
-    return 0;
+    return head_fwd(T, P, Q, P.X[nb], Q.X[nb], th, th_t, feat_out, st);
   }
   int res_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in, const float* ybar_t_in,
                    float* gout, float* dimage, const int64_t* idx, const float* coef, float mul, bool repack, bool stash,
@@ -1357,26 +1428,9 @@ struct Eng : mdd_engine {
     ActSet& P = sets[slot]; ActSet& Q = tn;
     ActSet& O = (!T && !stash) ? tn : P;  // where primal backward signals are written
     const int nb = (int)blks.size();
-    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
-    if (repack)
-      launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
-                            wf_t, wt_t, st);
     float* dw = O.dwf; float* dw_t = Q.dwf;
-    HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
-    if (!T && ybar_in != O.yB)
-      HIP_CHECK_RET(hipMemcpyAsync(O.yB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
-    const int hwf = xh[nb] * xh[nb];
-    if (nf.classes > 0) {
-      launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N,
-                          fpool, nf.classes, lin_main, st);
-      launch_linear_dgrad(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_hw, tp(th_t + off_hw),
-                          nullptr, N, fpool, nf.classes, lin_main, st);
-      launch_final_pool_bwd<AT>(O.XB[nb], T ? Q.XB[nb] : nullptr, O.hinB, T ? Q.hinB : nullptr, P.X[nb],
-                                T ? Q.X[nb] : nullptr, N, hwf, fpool, st, nf.relu != 0);
-    } else {
-      launch_final_pool_bwd<AT>(O.XB[nb], T ? Q.XB[nb] : nullptr, O.yB, T ? ybar_t_in : nullptr, P.X[nb],
-                                T ? Q.X[nb] : nullptr, N, hwf, feat, st, nf.relu != 0);
-    }
+    if (int rc = walk_bwd_begin(T, repack, O, ybar_in, gout, th, th_t, st)) return rc;
+    head_bwd(T, P, Q, O, ybar_t_in, P.X[nb], Q.X[nb], O.XB[nb], Q.XB[nb], gout, th, th_t, st);
     for (int b = nb - 1; b >= 0; --b) {
       const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
       BlockActs& oa = O.blk[b];
@@ -1386,34 +1440,12 @@ struct Eng : mdd_engine {
       launch_scale_act<AT>(T ? qa.C3B : oa.C3B, T ? xb_t : xb, nf.alpha, eout * B.cout, st);
       conv_bwd_w(T, convs[B.c3], oa.C3B, qa.C3B, pa.A2, qa.A2, dw, dw_t, gout, st);
       flush_w(st);
-      ConvEpi e3 = epi_act(T, oa.A2B, oa.C2B, qa.C2B, pa.C2, qa.C2, 1.f, nullptr, nullptr);
-      e3.act = ract;
-      conv_bwd_d(T, convs[B.c3], oa.C3B, qa.C3B, e3, st);
+      conv_bwd_d(T, convs[B.c3], oa.C3B, qa.C3B,
+                 epi_act(T, oa.A2B, oa.C2B, qa.C2B, pa.C2, qa.C2, 1.f, nullptr, nullptr, ract), st);
       conv_bwd_w(T, convs[B.c2], oa.C2B, qa.C2B, pa.A1, qa.A1, dw, dw_t, gout, st);
-      ConvEpi e2 = epi_act(T, oa.A1B, oa.C1B, qa.C1B, pa.C1, qa.C1, 1.f, nullptr, nullptr);
-      e2.act = ract;
-      conv_bwd_d(T, convs[B.c2], oa.C2B, qa.C2B, e2, st);
-      conv_bwd_w(T, convs[B.c1], oa.C1B, qa.C1B, P.A[b], Q.A[b], dw, dw_t, gout, st);
-      // shortcut branch
-      const AT* add1 = nullptr;
-      if (B.ds >= 0) {
-        const AT* dsin = B.stride == 2 ? pa.P : P.A[b];
-        const AT* dsin_t = B.stride == 2 ? qa.P : Q.A[b];
-        conv_bwd_w(T, convs[B.ds], xb, xb_t, dsin, dsin_t, dw, dw_t, gout, st);
-        conv_bwd_d(T, convs[B.ds], xb, xb_t, epi_lin(dsS, nullptr), st);
-        if (B.stride == 2) {
-          launch_avgpool2_bwd<AT>(dsF, dsS, N, B.hin, B.hin, B.cin, 2, st);
-          add1 = dsF;
-        } else {
-          add1 = dsS;
-        }
-      }
-      // conv1 dgrad + pre-activation chain rule + identity shortcut:  XB[b] = beta*1[X[b] > 0]*Abar (+ XB[b+1])
-      ConvEpi e1 = epi_act(T, oa.AinB, O.XB[b], Q.XB[b], P.X[b], Q.X[b], B.beta, add1,
-                           B.ds >= 0 ? nullptr : (T ? xb_t : xb));
-      e1.act = ract;
-      conv_bwd_d(T, convs[B.c1], oa.C1B, qa.C1B, e1, st);
-      if (b == 0) flush_w(st);
+      conv_bwd_d(T, convs[B.c2], oa.C2B, qa.C2B,
+                 epi_act(T, oa.A1B, oa.C1B, qa.C1B, pa.C1, qa.C1, 1.f, nullptr, nullptr, ract), st);
+      block_input_bwd(T, b, P, Q, O, dw, dw_t, gout, st);
     }
     // stem: max-pool backward (gather through the window index), then the 7x7 conv's weight and image gradients
     const ConvL& L0 = convs[stem[0]];
@@ -1425,12 +1457,7 @@ struct Eng : mdd_engine {
       launch_img_scatter_grad<AT>(dimage, x0b, idx, coef, mul, N, 3, S, S, 8, st);
     }
     conv_bwd_w(T, stem_col, O.CsB[0], Q.CsB[0], P.COL, nullptr, dw, dw_t, gout, st);
-    flush_w(st, MAIN_TAIL);
-    join(st);
-    launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw,
-                       T ? dw_t : nullptr, gout, st);
-    POST_WALK("res_backward");
-    return 0;
+    return walk_bwd_end(T, dw, dw_t, gout, th, th_t, st);
   }
 
   // ================================================================== NF-RegNet image encoder (timm nf_regnet_b1)
@@ -1442,36 +1469,18 @@ struct Eng : mdd_engine {
                   float* feat_out, hipStream_t st) {
     ActSet& P = sets[slot]; ActSet& Q = tn;
     const int nb = (int)blks.size();
-    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
-    launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
-                          wf_t, wt_t, st);
-    if (!T) launch_img_gather_nhwc<AT>(P.X0, image, idx, N, 3, S, S, 8, st);
+    walk_fwd_begin(T, P, th, th_t, image, idx, st);
     conv_fwd(T, convs[stem[0]], P.X0, nullptr, P.X[0], Q.X[0], P.A[0], Q.A[0], blks[0].beta, th, th_t, st);
     for (int b = 0; b < nb; ++b) {
       const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
       const AT *a = P.A[b], *a_t = Q.A[b];
       const AT *sc = P.X[b], *sc_t = Q.X[b];
-      bool sc_forked = false;
-      if (B.ds >= 0) {
-        // the shortcut (avg-pool + 1x1 conv) only meets the residual branch at the residual sum: side stream
-        hipStream_t ss = st;
-        if (use_side) { fork(st); ss = side; sc_forked = true; }
-        const AT *din = a, *din_t = a_t;
-        if (B.stride == 2) {
-          launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
-          din = pa.P; din_t = qa.P;
-        }
-        conv_fwd(T, convs[B.ds], din, din_t, pa.SC, qa.SC, nullptr, nullptr, 1.f, th, th_t, ss);
-        sc = pa.SC; sc_t = qa.SC;
-      }
-      const int hw = B.hout * B.hout, c = B.mid, rd = B.se.rd;
+      const bool sc_forked = shortcut_fwd(T, B, pa, qa, a, a_t, th, th_t, st, sc, sc_t);
+      const int hw = B.hout * B.hout, c = B.mid;
       conv_fwd(T, convs[B.c1], a, a_t, pa.C1, qa.C1, pa.A1, qa.A1, 1.f, th, th_t, st);
       conv_fwd(T, convs[B.c2], pa.A1, qa.A1, pa.C2, qa.C2, nullptr, nullptr, 1.f, th, th_t, st);
       launch_pool_mean<AT>(T ? qa.q : pa.q, T ? qa.C2 : pa.C2, N, hw, c, st);
-      launch_linear_fwd(pa.h, T ? qa.h : nullptr, pa.q, T ? qa.q : nullptr, th + B.se.off_w1, tp(th_t + B.se.off_w1),
-                        th + B.se.off_b1, tp(th_t + B.se.off_b1), N, c, rd, 1, lin_main, st);
-      launch_linear_fwd(pa.gate, T ? qa.gate : nullptr, pa.h, T ? qa.h : nullptr, th + B.se.off_w2,
-                        tp(th_t + B.se.off_w2), th + B.se.off_b2, tp(th_t + B.se.off_b2), N, rd, c, 2, lin_main, st);
+      se_mlp_fwd(T, B, pa, qa, pa.q, qa.q, th, th_t, st);
       launch_mid_se_apply<AT>(pa.A2, T ? qa.A2 : nullptr, pa.C2, T ? qa.C2 : nullptr, pa.gate, T ? qa.gate : nullptr,
                               nf.attn_gain, N, hw, c, st);
       conv_fwd(T, convs[B.c3], pa.A2, qa.A2, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
@@ -1481,16 +1490,9 @@ struct Eng : mdd_engine {
                             lastb ? nullptr : P.A[b + 1], (T && !lastb) ? Q.A[b + 1] : nullptr, nf.alpha,
                             lastb ? 1.f : blks[b + 1].beta, (int64_t)N * hw * B.cout, st);
     }
-    // final conv on the raw stream, final_act (SiLU) + global average pool, then the classifier (small-batch fp32 linear)
-    conv_fwd(T, convs[fin], P.X[nb], Q.X[nb], P.CF, Q.CF, nullptr, nullptr, 1.f, th, th_t, st);
-    const int hwf = xh[nb] * xh[nb];
-    launch_final_pool<AT>(P.hin, T ? Q.hin : nullptr, P.CF, T ? Q.CF : nullptr, N, hwf, fpool, st);
-    launch_linear_fwd(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_hw, tp(th_t + off_hw),
-                      th + off_hb, tp(th_t + off_hb), N, fpool, nf.classes, 0, lin_main, st);
-    if (!T && feat_out && feat_out != P.y)
-      HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
-    POST_WALK("reg_forward");
-    return 0;
+    // final conv on the raw stream, then the head
+    final_conv_fwd(T, P, Q, th, th_t, st);
+    return head_fwd(T, P, Q, P.CF, Q.CF, th, th_t, feat_out, st);
   }
   int reg_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in, const float* ybar_t_in,
                    float* gout, float* dimage, const int64_t* idx, const float* coef, float mul, bool repack, bool stash,
@@ -1498,28 +1500,15 @@ struct Eng : mdd_engine {
     ActSet& P = sets[slot]; ActSet& Q = tn;
     ActSet& O = (!T && !stash) ? tn : P;  // where primal backward signals are written
     const int nb = (int)blks.size();
-    auto tp = [&](const float* q) { return T ? q : (const float*)nullptr; };
-    if (repack)
-      launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
-                            wf_t, wt_t, st);
     float* dw = O.dwf; float* dw_t = Q.dwf;
-    HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
-    if (!T && ybar_in != O.yB)
-      HIP_CHECK_RET(hipMemcpyAsync(O.yB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
-    const int hwf = xh[nb] * xh[nb];
-    launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N,
-                        fpool, nf.classes, lin_main, st);
-    launch_linear_dgrad(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_hw, tp(th_t + off_hw),
-                        nullptr, N, fpool, nf.classes, lin_main, st);
-    launch_final_pool_bwd<AT>(O.CFB, T ? Q.CFB : nullptr, O.hinB, T ? Q.hinB : nullptr, P.CF, T ? Q.CF : nullptr, N, hwf,
-                              fpool, st);
-    conv_bwd_w(T, convs[fin], O.CFB, Q.CFB, P.X[nb], Q.X[nb], dw, dw_t, gout, st);
-    conv_bwd_d(T, convs[fin], O.CFB, Q.CFB, epi_lin(T ? Q.XB[nb] : O.XB[nb], nullptr), st);
+    if (int rc = walk_bwd_begin(T, repack, O, ybar_in, gout, th, th_t, st)) return rc;
+    head_bwd(T, P, Q, O, ybar_t_in, P.CF, Q.CF, O.CFB, Q.CFB, gout, th, th_t, st);
+    final_conv_bwd(T, P, Q, O, dw, dw_t, gout, st);
     for (int b = nb - 1; b >= 0; --b) {
       const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
       BlockActs& oa = O.blk[b];
       const AT *xb = O.XB[b + 1], *xb_t = Q.XB[b + 1];
-      const int hw = B.hout * B.hout, c = B.mid, rd = B.se.rd;
+      const int hw = B.hout * B.hout, c = B.mid;
       const int64_t eout = (int64_t)N * hw;
       // x' = alpha*c3 + shortcut: conv3's output gradient is alpha times the block output's
       launch_scale_act<AT>(T ? qa.C3B : oa.C3B, T ? xb_t : xb, nf.alpha, eout * B.cout, st);
@@ -1531,44 +1520,13 @@ struct Eng : mdd_engine {
       // the pooled path's share qbar / hw
       launch_mid_se_bwd<AT>(oa.zB, T ? qa.zB : nullptr, oa.C2B, T ? qa.C2B : nullptr, pa.C2, T ? qa.C2 : nullptr, oa.A2B,
                             T ? qa.A2B : nullptr, pa.gate, T ? qa.gate : nullptr, nf.attn_gain, N, hw, c, st);
-      launch_linear_dgrad(oa.hB, T ? qa.hB : nullptr, oa.zB, T ? qa.zB : nullptr, th + B.se.off_w2,
-                          tp(th_t + B.se.off_w2), pa.h, N, rd, c, lin_main, st);
-      launch_linear_dgrad(oa.qB, T ? qa.qB : nullptr, oa.hB, T ? qa.hB : nullptr, th + B.se.off_w1,
-                          tp(th_t + B.se.off_w1), nullptr, N, c, rd, lin_main, st);
+      se_mlp_bwd(T, B, oa, pa, qa, oa.qB, qa.qB, th, th_t, st);
       launch_add_pooled<AT>(T ? qa.C2B : oa.C2B, T ? qa.qB : oa.qB, 1.f / (float)hw, N, hw, c, st);
-      {
-        const float *zB = oa.zB, *zB_t = T ? qa.zB : nullptr, *hh = pa.h, *hh_t = T ? qa.h : nullptr;
-        const float *hB = oa.hB, *hB_t = T ? qa.hB : nullptr, *qq = pa.q, *qq_t = T ? qa.q : nullptr;
-        float *gw2 = gout + B.se.off_w2, *gb2 = gout + B.se.off_b2, *gw1 = gout + B.se.off_w1, *gb1 = gout + B.se.off_b1;
-        const int n_ = N;
-        wq.push_back([=](hipStream_t ws_) {
-          launch_linear_wgrad(gw2, gb2, zB, zB_t, hh, hh_t, n_, rd, c, wlin(), ws_);
-          launch_linear_wgrad(gw1, gb1, hB, hB_t, qq, qq_t, n_, c, rd, wlin(), ws_);
-        });
-      }
+      queue_se_wgrads(T, B, oa, pa, qa, pa.q, qa.q, gout);
       conv_bwd_w(T, convs[B.c2], oa.C2B, qa.C2B, pa.A1, qa.A1, dw, dw_t, gout, st);
       conv_bwd_d(T, convs[B.c2], oa.C2B, qa.C2B,
                  epi_act(T, oa.A1B, oa.C1B, qa.C1B, pa.C1, qa.C1, 1.f, nullptr, nullptr), st);
-      conv_bwd_w(T, convs[B.c1], oa.C1B, qa.C1B, P.A[b], Q.A[b], dw, dw_t, gout, st);
-      // shortcut branch
-      const AT* add1 = nullptr;
-      if (B.ds >= 0) {
-        const AT* dsin = B.stride == 2 ? pa.P : P.A[b];
-        const AT* dsin_t = B.stride == 2 ? qa.P : Q.A[b];
-        conv_bwd_w(T, convs[B.ds], xb, xb_t, dsin, dsin_t, dw, dw_t, gout, st);
-        conv_bwd_d(T, convs[B.ds], xb, xb_t, epi_lin(dsS, nullptr), st);
-        if (B.stride == 2) {
-          launch_avgpool2_bwd<AT>(dsF, dsS, N, B.hin, B.hin, B.cin, 2, st);
-          add1 = dsF;
-        } else {
-          add1 = dsS;
-        }
-      }
-      // conv1 dgrad + pre-activation chain rule + identity shortcut:  XB[b] = beta*silu'(X[b])*Abar (+ XB[b+1])
-      conv_bwd_d(T, convs[B.c1], oa.C1B, qa.C1B,
-                 epi_act(T, oa.AinB, O.XB[b], Q.XB[b], P.X[b], Q.X[b], B.beta, add1,
-                         B.ds >= 0 ? nullptr : (T ? xb_t : xb)), st);
-      if (b == 0) flush_w(st);
+      block_input_bwd(T, b, P, Q, O, dw, dw_t, gout, st);
     }
     // stem: the conv's raw output is the stream X[0], its gradient XB[0]
     const ConvL& L0 = convs[stem[0]];
@@ -1578,29 +1536,17 @@ struct Eng : mdd_engine {
       launch_img_scatter_grad<AT>(dimage, x0b, idx, coef, mul, N, 3, S, S, 8, st);
     }
     conv_bwd_w(T, L0, O.XB[0], Q.XB[0], P.X0, nullptr, dw, dw_t, gout, st);
-    flush_w(st, MAIN_TAIL);
-    join(st);
-    launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw,
-                       T ? dw_t : nullptr, gout, st);
-    POST_WALK("reg_backward");
-    return 0;
+    return walk_bwd_end(T, dw, dw_t, gout, th, th_t, st);
   }
 
-  // ------------------------------------------------------------------ image encoder: F / T-fwd
-  int img_forward(bool T, int slot, const float* th, const float* th_t, const float* image,
-                  const int64_t* idx, float* feat_out, hipStream_t st) override {
-    CHECK_ARG(base, "workspace not bound");
-    DevGuard guard(device_id);
-    CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
-    select_prec(T, false);
-    if (is_vit) return vit_forward(T, slot, th, th_t, image, idx, feat_out, st);
-    if (walker == 1) return res_forward(T, slot, th, th_t, image, idx, feat_out, st);
-    if (walker == 2) return reg_forward(T, slot, th, th_t, image, idx, feat_out, st);
+  // ================================================================== NFNet image encoder (timm nfnet_l0 / l1)
+  // stem of four 3x3 convs -> blocks {a = beta*silu(x); shortcut = x or downsample(a); c3 = conv3(silu(conv2b(silu(
+  // conv2(silu(conv1(a))))))); x' = attn_gain*alpha*gate(c3)*c3 + shortcut} -> final conv -> silu -> global average pool
+  int nfnet_forward(bool T, int slot, const float* th, const float* th_t, const float* image, const int64_t* idx,
+                    float* feat_out, hipStream_t st) {
     ActSet& P = sets[slot]; ActSet& Q = tn;
-    int nb = (int)blks.size();
-    launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
-                          wf_t, wt_t, st);
-    if (!T) launch_img_gather_nhwc<AT>(P.X0, image, idx, N, 3, S, S, 8, st);
+    const int nb = (int)blks.size();
+    walk_fwd_begin(T, P, th, th_t, image, idx, st);
     const AT* in = P.X0; const AT* in_t = nullptr;
     for (int i = 0; i < 4; ++i) {
       bool last = i == 3;
@@ -1612,74 +1558,52 @@ struct Eng : mdd_engine {
     const float ga = nf.attn_gain * nf.alpha;
     for (int b = 0; b < nb; ++b) {
       const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
-      const AT *x = P.X[b], *x_t = Q.X[b], *a = P.A[b], *a_t = Q.A[b];
-      const AT *sc = x, *sc_t = x_t;
-      bool sc_forked = false;
-      if (B.ds >= 0) {
-        // the shortcut (avg-pool + 1x1 conv) only meets the residual branch at the SE apply: it runs on
-        // the side stream, which is idle during forward passes
-        hipStream_t ss = st;
-        if (use_side) { fork(st); ss = side; sc_forked = true; }
-        const AT *din = a, *din_t = a_t;
-        if (B.stride == 2) {
-          launch_avgpool2<AT>(T ? qa.P : pa.P, T ? a_t : a, N, B.hin, B.hin, B.cin, 2, ss);
-          din = pa.P; din_t = qa.P;
-        }
-        conv_fwd(T, convs[B.ds], din, din_t, pa.SC, qa.SC, nullptr, nullptr, 1.f, th, th_t, ss);
-        sc = pa.SC; sc_t = qa.SC;
-      }
+      const AT *a = P.A[b], *a_t = Q.A[b];
+      const AT *sc = P.X[b], *sc_t = Q.X[b];
+      const bool sc_forked = shortcut_fwd(T, B, pa, qa, a, a_t, th, th_t, st, sc, sc_t);
       conv_fwd(T, convs[B.c1], a, a_t, pa.C1, qa.C1, pa.A1, qa.A1, 1.f, th, th_t, st);
       conv_fwd(T, convs[B.c2], pa.A1, qa.A1, pa.C2, qa.C2, pa.A2, qa.A2, 1.f, th, th_t, st);
       conv_fwd(T, convs[B.c2b], pa.A2, qa.A2, pa.C2b, qa.C2b, pa.A2b, qa.A2b, 1.f, th, th_t, st);
-      int hw = B.hout * B.hout, c = B.se.c, rd = B.se.rd;
+      const int hw = B.hout * B.hout, c = B.se.c;
+      const ConvL& L3 = convs[B.c3];
       // Squeeze-excite gate.  conv3 is a pointwise (linear) conv, so the pooled conv3 output is conv3 applied to
       // the pooled MID-channel activation: p = W3_hat q + b3 with q = mean_hw(A2b) -- a quarter of the bytes of
       // pooling C3, and the whole gate chain (pool, three small-batch linears) no longer waits for conv3: it runs
-      // on the side stream beside it and meets the main stream at the SE apply.
+      // on the gate stream beside it and meets the main stream at the SE apply.
       // (with the apply fused into conv3's epilogue, below, conv3 waits for the gate anyway: the chain then runs on the
       // main stream in front of it and the two cross-stream events of the block are saved)
-      const bool fuse3 = se_fused_enabled() && conv_gemm_supports_se(gfwd(convs[B.c3]), (int)sizeof(AT));
+      const bool fuse3 = se_fused_enabled() && conv_gemm_supports_se(gfwd(L3), (int)sizeof(AT));
       bool g_forked = false;
-      {
-        hipStream_t gs = st;
-        if (use_side && gstream && !fuse3) { fork_to(gstream, st); gs = gstream; g_forked = true; }
-        launch_pool_mean<AT>(T ? qa.q : pa.q, T ? qa.A2b : pa.A2b, N, hw, B.mid, gs);
-        const ConvL& L3 = convs[B.c3];
-        launch_linear_fwd_w<AT>(pa.p, T ? qa.p : nullptr, pa.q, T ? qa.q : nullptr, wf + L3.off_p,
-                                T ? wf_t + L3.off_p : nullptr, th + L3.off_b, T ? th_t + L3.off_b : nullptr, N,
-                                B.mid, c, 1.f, gs);
-        launch_linear_fwd(pa.h, T ? qa.h : nullptr, pa.p, T ? qa.p : nullptr, th + B.se.off_w1,
-                          T ? th_t + B.se.off_w1 : nullptr, th + B.se.off_b1,
-                          T ? th_t + B.se.off_b1 : nullptr, N, c, rd, 1, lin_main, gs);
-        launch_linear_fwd(pa.gate, T ? qa.gate : nullptr, pa.h, T ? qa.h : nullptr, th + B.se.off_w2,
-                          T ? th_t + B.se.off_w2 : nullptr, th + B.se.off_b2,
-                          T ? th_t + B.se.off_b2 : nullptr, N, rd, c, 2, lin_main, gs);
-      }
-      bool lastb = b == nb - 1;
-      const ConvL& L3f = convs[B.c3];
+      hipStream_t gs = st;
+      if (use_side && gstream && !fuse3) { fork_to(gstream, st); gs = gstream; g_forked = true; }
+      launch_pool_mean<AT>(T ? qa.q : pa.q, T ? qa.A2b : pa.A2b, N, hw, B.mid, gs);
+      launch_linear_fwd_w<AT>(pa.p, T ? qa.p : nullptr, pa.q, T ? qa.q : nullptr, wf + L3.off_p,
+                              T ? wf_t + L3.off_p : nullptr, th + L3.off_b, tp(T, th_t + L3.off_b), N, B.mid, c, 1.f, gs);
+      se_mlp_fwd(T, B, pa, qa, pa.p, qa.p, th, th_t, gs);
+      const bool lastb = b == nb - 1;
       if (fuse3) {
         // the gate no longer depends on conv3, so conv3's epilogue applies it: C3 is stashed as before, and X' (and the
         // next block's pre-activation A') are written from the accumulator tile instead of by a second kernel that
         // re-reads C3.  conv3 now waits for the gate chain (in front of it on this stream) and for the shortcut, which
         // its epilogue reads.
         if (sc_forked) join(st);
-        ConvGeom g = gfwd(L3f);
+        ConvGeom g = gfwd(L3);
         ConvEpi e; memset(&e, 0, sizeof e);
         e.beta = lastb ? 1.f : blks[b + 1].beta;
         e.ib = pa.gate; e.ib_t = T ? qa.gate : nullptr; e.ib_mul = ga; e.ib_hw = hw;
         e.add1 = sc; e.add2 = T ? sc_t : nullptr;
         if (!T) {
-          e.mode = EPI_FWD_SE; e.bias = th + L3f.off_b; e.out_raw = pa.C3; e.out_x = P.X[b + 1];
+          e.mode = EPI_FWD_SE; e.bias = th + L3.off_b; e.out_raw = pa.C3; e.out_x = P.X[b + 1];
           e.out_act = lastb ? nullptr : P.A[b + 1];
-          gemm(L3f, g, pa.A2b, wf + L3f.off_p, nullptr, nullptr, e, st);
+          gemm(L3, g, pa.A2b, wf + L3.off_p, nullptr, nullptr, e, st);
         } else {
-          e.mode = EPI_FWD_SE_T; e.bias_t = th_t + L3f.off_b; e.c = pa.C3; e.out_raw = qa.C3; e.out_x = Q.X[b + 1];
+          e.mode = EPI_FWD_SE_T; e.bias_t = th_t + L3.off_b; e.c = pa.C3; e.out_raw = qa.C3; e.out_x = Q.X[b + 1];
           e.out_act = lastb ? nullptr : Q.A[b + 1];
-          gemm(L3f, g, qa.A2b, wf + L3f.off_p, pa.A2b, wf_t + L3f.off_p, e, st);
+          gemm(L3, g, qa.A2b, wf + L3.off_p, pa.A2b, wf_t + L3.off_p, e, st);
         }
         continue;
       }
-      conv_fwd(T, convs[B.c3], pa.A2b, qa.A2b, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
+      conv_fwd(T, L3, pa.A2b, qa.A2b, pa.C3, qa.C3, nullptr, nullptr, 1.f, th, th_t, st);
       if (sc_forked) join(st);
       if (g_forked) join_from(gstream, st);
       launch_se_apply<AT>(pa.C3, T ? qa.C3 : nullptr, pa.gate, T ? qa.gate : nullptr, sc,
@@ -1687,52 +1611,28 @@ struct Eng : mdd_engine {
                           lastb ? nullptr : P.A[b + 1], (T && !lastb) ? Q.A[b + 1] : nullptr, ga,
                           lastb ? 1.f : blks[b + 1].beta, N, hw, c, st);
     }
-    conv_fwd(T, convs[fin], P.X[nb], Q.X[nb], P.CF, Q.CF, nullptr, nullptr, 1.f, th, th_t, st);
+    final_conv_fwd(T, P, Q, th, th_t, st);
     if (use_side && gstream) join_from(gstream, st);     // everything enqueued on the gate stream
-    int hwf = xh[nb] * xh[nb];
-    launch_final_pool<AT>(P.y, T ? feat_out : nullptr, P.CF, T ? Q.CF : nullptr, N, hwf, feat, st);
-    if (!T && feat_out && feat_out != P.y)
-      HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.y, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
-    POST_WALK("img_forward");
-    return 0;
+    return head_fwd(T, P, Q, P.CF, Q.CF, th, th_t, feat_out, st);
   }
-
-  // ------------------------------------------------------------------ image encoder: B / T-bwd
-  int img_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in,
-                   const float* ybar_t_in, float* gout, float* dimage, const int64_t* idx,
-                   const float* coef, float mul, bool repack, bool stash, hipStream_t st) override {
-    CHECK_ARG(base, "workspace not bound");
-    DevGuard guard(device_id);
-    CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
-    select_prec(T, true);
-    if (is_vit) return vit_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
-    if (walker == 1) return res_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
-    if (walker == 2) return reg_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+  int nfnet_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in, const float* ybar_t_in,
+                     float* gout, float* dimage, const int64_t* idx, const float* coef, float mul, bool repack, bool stash,
+                     hipStream_t st) {
     ActSet& P = sets[slot]; ActSet& Q = tn;
     ActSet& O = (!T && !stash) ? tn : P;  // where primal backward signals are written
-    int nb = (int)blks.size();
-    if (repack) {
-      launch_ws_forward<AT>(d_descs, (int)descs.size(), total_rows, total_tiles, th, T ? th_t : nullptr, wf, wt,
-                            wf_t, wt_t, st);
-    }
+    const int nb = (int)blks.size();
     float* dw = O.dwf; float* dw_t = Q.dwf;
-    // (no zero-fill of dwf: every conv's two-phase weight gradient overwrites its whole packed slice)
-    HIP_CHECK_RET(hipMemsetAsync(gout, 0, P_img * 4, st));
-    if (!T && ybar_in != O.yB)
-      HIP_CHECK_RET(hipMemcpyAsync(O.yB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
+    if (int rc = walk_bwd_begin(T, repack, O, ybar_in, gout, th, th_t, st)) return rc;
     const float ga = nf.attn_gain * nf.alpha;
-    int hwf = xh[nb] * xh[nb];
-    launch_final_pool_bwd<AT>(O.CFB, T ? Q.CFB : nullptr, O.yB, T ? ybar_t_in : nullptr, P.CF,
-                              T ? Q.CF : nullptr, N, hwf, feat, st);
-    conv_bwd_w(T, convs[fin], O.CFB, Q.CFB, P.X[nb], Q.X[nb], dw, dw_t, gout, st);
-    conv_bwd_d(T, convs[fin], O.CFB, Q.CFB, epi_lin(T ? Q.XB[nb] : O.XB[nb], nullptr), st);
+    head_bwd(T, P, Q, O, ybar_t_in, P.CF, Q.CF, O.CFB, Q.CFB, gout, th, th_t, st);
+    final_conv_bwd(T, P, Q, O, dw, dw_t, gout, st);
     for (int b = nb - 1; b >= 0; --b) {
       const Blk& B = blks[b]; BlockActs& pa = P.blk[b]; BlockActs& qa = Q.blk[b];
       BlockActs& oa = O.blk[b];
       const AT *xb = O.XB[b + 1], *xb_t = Q.XB[b + 1];
-      int hw = B.hout * B.hout, c = B.se.c, rd = B.se.rd;
+      const int hw = B.hout * B.hout, c = B.se.c;
       // squeeze-excite backward.  One pass over (xb, C3) gives the gate gradient AND conv3's output gradient
-      // C3B = ga * gate * xb: with the pooled vector taken from the mid channels (img_forward) the pooled path's
+      // C3B = ga * gate * xb: with the pooled vector taken from the mid channels (nfnet_forward) the pooled path's
       // gradient no longer goes through C3 -- it reaches conv3's weights as the small outer product pb^T q, its
       // bias as sum_n pb, and the residual branch as the per-image vector qb / hw added in conv3's data-gradient
       // epilogue.
@@ -1743,25 +1643,16 @@ struct Eng : mdd_engine {
       conv_bwd_w(T, convs[B.c3], oa.C3B, qa.C3B, pa.A2b, qa.A2b, dw, dw_t, gout, st);
       flush_w(st);
       const ConvL& L3 = convs[B.c3];
+      queue_se_wgrads(T, B, oa, pa, qa, pa.p, qa.p, gout);
       {
-        const float *zB = oa.zB, *zB_t = T ? qa.zB : nullptr, *hh = pa.h, *hh_t = T ? qa.h : nullptr;
-        const float *hB = oa.hB, *hB_t = T ? qa.hB : nullptr, *pp = pa.p, *pp_t = T ? qa.p : nullptr;
         const float *pB = oa.pB, *pB_t = T ? qa.pB : nullptr, *qq = pa.q, *qq_t = T ? qa.q : nullptr;
-        float *gw2 = gout + B.se.off_w2, *gb2 = gout + B.se.off_b2, *gw1 = gout + B.se.off_w1,
-              *gb1 = gout + B.se.off_b1, *gw3 = (T ? dw_t : dw) + L3.off_p, *gb3 = gout + L3.off_b;
+        float *gw3 = (T ? dw_t : dw) + L3.off_p, *gb3 = gout + L3.off_b;
         const int n_ = N, mid_ = B.mid;
-        wq.push_back([=](hipStream_t ws_) {
-          launch_linear_wgrad(gw2, gb2, zB, zB_t, hh, hh_t, n_, rd, c, wlin(), ws_);
-          launch_linear_wgrad(gw1, gb1, hB, hB_t, pp, pp_t, n_, c, rd, wlin(), ws_);
-          // after conv3's own weight gradient (queued above: same stream, in order) has overwritten its slice
-          launch_linear_wgrad_accum(gw3, gb3, pB, pB_t, qq, qq_t, n_, mid_, c, ws_);
-        });
+        // the pooled path's share of conv3's weight gradient, after conv3's own weight gradient (queued above: same
+        // stream, in order) has overwritten its slice
+        wq.push_back([=](hipStream_t ws_) { launch_linear_wgrad_accum(gw3, gb3, pB, pB_t, qq, qq_t, n_, mid_, c, ws_); });
       }
-      launch_linear_dgrad(oa.hB, T ? qa.hB : nullptr, oa.zB, T ? qa.zB : nullptr,
-                          th + B.se.off_w2, T ? th_t + B.se.off_w2 : nullptr, pa.h, N, rd, c,
-                          lin_main, st);
-      launch_linear_dgrad(oa.pB, T ? qa.pB : nullptr, oa.hB, T ? qa.hB : nullptr, th + B.se.off_w1,
-                          T ? th_t + B.se.off_w1 : nullptr, nullptr, N, c, rd, lin_main, st);
+      se_mlp_bwd(T, B, oa, pa, qa, oa.pB, qa.pB, th, th_t, st);
       launch_linear_fwd_w<AT>(oa.qB, T ? qa.qB : nullptr, oa.pB, T ? qa.pB : nullptr, wt + L3.off_p,
                               T ? wt_t + L3.off_p : nullptr, nullptr, nullptr, N, c, B.mid, 1.f, st);
       // residual branch
@@ -1776,26 +1667,7 @@ struct Eng : mdd_engine {
       conv_bwd_w(T, convs[B.c2], oa.C2B, qa.C2B, pa.A1, qa.A1, dw, dw_t, gout, st);
       conv_bwd_d(T, convs[B.c2], oa.C2B, qa.C2B,
                  epi_act(T, oa.A1B, oa.C1B, qa.C1B, pa.C1, qa.C1, 1.f, nullptr, nullptr), st);
-      conv_bwd_w(T, convs[B.c1], oa.C1B, qa.C1B, P.A[b], Q.A[b], dw, dw_t, gout, st);
-      // shortcut branch
-      const AT* add1 = nullptr;
-      if (B.ds >= 0) {
-        const AT* dsin = B.stride == 2 ? pa.P : P.A[b];
-        const AT* dsin_t = B.stride == 2 ? qa.P : Q.A[b];
-        conv_bwd_w(T, convs[B.ds], xb, xb_t, dsin, dsin_t, dw, dw_t, gout, st);
-        conv_bwd_d(T, convs[B.ds], xb, xb_t, epi_lin(dsS, nullptr), st);
-        if (B.stride == 2) {
-          launch_avgpool2_bwd<AT>(dsF, dsS, N, B.hin, B.hin, B.cin, 2, st);
-          add1 = dsF;
-        } else {
-          add1 = dsS;
-        }
-      }
-      // conv1 dgrad + pre-activation chain rule + identity shortcut:  XB[b] = beta*silu'(X[b])*Abar (+ XB[b+1])
-      conv_bwd_d(T, convs[B.c1], oa.C1B, qa.C1B,
-                 epi_act(T, oa.AinB, O.XB[b], Q.XB[b], P.X[b], Q.X[b], B.beta, add1,
-                         B.ds >= 0 ? nullptr : (T ? xb_t : xb)), st);
-      if (b == 0) flush_w(st);
+      block_input_bwd(T, b, P, Q, O, dw, dw_t, gout, st);
     }
     // stem (conv4 output is the raw stream X[0]; its grad is XB[0])
     conv_bwd_w(T, convs[stem[3]], O.XB[0], Q.XB[0], P.As[2], Q.As[2], dw, dw_t, gout, st);
@@ -1827,12 +1699,36 @@ struct Eng : mdd_engine {
     // the high-resolution layers' weight gradients queued and would otherwise be waited for
     conv_bwd_w(T, convs[stem[1]], O.CsB[1], Q.CsB[1], P.As[0], Q.As[0], dw, dw_t, gout, st);
     conv_bwd_w(T, convs[stem[0]], O.CsB[0], Q.CsB[0], P.X0, nullptr, dw, dw_t, gout, st);
-    flush_w(st, MAIN_TAIL);
-    join(st);
-    launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw,
-                       T ? dw_t : nullptr, gout, st);
-    POST_WALK("img_backward");
-    return 0;
+    return walk_bwd_end(T, dw, dw_t, gout, th, th_t, st);
+  }
+
+  // ------------------------------------------------------------------ image encoder: F / T-fwd and B / T-bwd entry points
+  int img_forward(bool T, int slot, const float* th, const float* th_t, const float* image,
+                  const int64_t* idx, float* feat_out, hipStream_t st) override {
+    CHECK_ARG(base, "workspace not bound");
+    DevGuard guard(device_id);
+    CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
+    select_prec(T, false);
+    if (is_vit) return vit_forward(T, slot, th, th_t, image, idx, feat_out, st);
+    switch (walker) {
+      case 1: return res_forward(T, slot, th, th_t, image, idx, feat_out, st);
+      case 2: return reg_forward(T, slot, th, th_t, image, idx, feat_out, st);
+      default: return nfnet_forward(T, slot, th, th_t, image, idx, feat_out, st);
+    }
+  }
+  int img_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in,
+                   const float* ybar_t_in, float* gout, float* dimage, const int64_t* idx,
+                   const float* coef, float mul, bool repack, bool stash, hipStream_t st) override {
+    CHECK_ARG(base, "workspace not bound");
+    DevGuard guard(device_id);
+    CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
+    select_prec(T, true);
+    if (is_vit) return vit_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+    switch (walker) {
+      case 1: return res_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+      case 2: return reg_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+      default: return nfnet_backward(T, slot, th, th_t, ybar_in, ybar_t_in, gout, dimage, idx, coef, mul, repack, stash, st);
+    }
   }
 
   // ------------------------------------------------------------------ text projection head
@@ -1856,7 +1752,7 @@ struct Eng : mdd_engine {
                   tt(t_lb), N, feat, 1e-5f, st);
     if (!T && feat_out && feat_out != P.ty)
       HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.ty, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
-    POST_WALK("txt_forward");
+    POST_WALK();
     return 0;
   }
   std::vector<const float*> slot_mask_ = std::vector<const float*>(65, nullptr);
@@ -1889,7 +1785,7 @@ struct Eng : mdd_engine {
                           tt(t_pw), nullptr, N, Dt, feat, lin_txt, st);
       launch_scatter_rows_axpy(dtext, xb, idx, coef, mul, N, Dt, st);
     }
-    POST_WALK("txt_backward");
+    POST_WALK();
     return 0;
   }
 
@@ -1903,7 +1799,7 @@ struct Eng : mdd_engine {
                                nullptr, scale_dev, scale_const, N, feat, st);
     else launch_contrastive(w, nullptr, nullptr, nullptr, nullptr, xb, yb, sb, x, y, x_t, y_t,
                             scale_dev, scale_const, N, feat, st);
-    POST_WALK("contrastive");
+    POST_WALK();
     return 0;
   }
 
@@ -1995,7 +1891,7 @@ struct Eng : mdd_engine {
     }
     join_from(ts, st);
     launch_d2f(a->grad_lr, dsc + 4, 1.f, 0, 2, st);
-    POST_WALK("unrolled_match");
+    POST_WALK();
     return 0;
   }
 };
