@@ -66,9 +66,10 @@ typedef struct mdd_config {
 
 const char* mdd_last_error(void);
 /* ABI version of this header: 2 = round 2 (mdd_config.keep_steps, MDD_DTYPE_BF16X2 / _F32_BF16OPS,
- * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se; 9 = + mdd_set_se_fused; 10 = + mdd_op_linear, mdd_op_pool_se.  A binding built against another version
+ * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se; 9 = + mdd_set_se_fused; 10 = + mdd_op_linear, mdd_op_pool_se; 11 = + mdd_op_weight_std, mdd_op_text_head,
+ * mdd_op_contrastive refuses what its kernels cannot take.  A binding built against another version
  * must refuse to load. */
-#define MDD_ABI_VERSION 10
+#define MDD_ABI_VERSION 11
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
  * pipelined kernels; 0 routes them to the general kernels instead (process-wide; returns the previous setting).  For the
@@ -148,7 +149,10 @@ int mdd_contrastive_tangent(mdd_engine* e, const float* x_dev, const float* y_de
 /* The same head without an engine, for any row count: sample-sharded runs (SURVEY 8e mode B, what
  * `--distributed` / nn.DataParallel does at distill.py:443-445, 515-517) evaluate it on the all-gathered
  * [n, d] features of every rank.  x_dot/y_dot NULL: loss, xbar, ybar, sbar; non-NULL: their directional
- * derivatives into the same output pointers (loss unused).  work: mdd_op_contrastive_workspace_floats(n, d). */
+ * derivatives into the same output pointers (loss unused).  work: mdd_op_contrastive_workspace_floats(n, d).
+ * Refused with "invalid argument" before anything is launched (mdd_contrastive / _tangent refuse the same): d > 4096 (the
+ * feature-gradient kernel keeps 16 x 256 features of a row in registers), n > 4092 (the cross-entropy kernel's (4 n + 16)
+ * floats of LDS must fit the 64 KiB a workgroup may ask for), an n whose n * n does not fit an int. */
 int64_t mdd_op_contrastive_workspace_floats(int n, int d);
 int mdd_op_contrastive(int n, int d, const float* x_dev, const float* y_dev, const float* x_dot_dev,
                        const float* y_dot_dev, const float* scale_dev, float scale_const, float* work_dev,
@@ -279,6 +283,44 @@ int mdd_op_linear(int form, int route, int wdtype, int n, int k, int j, int act,
 int mdd_op_pool_se(int dtype, int op, int n, int h, int w, int c, float ga, float beta, const void* a, const void* a_t,
                    const void* b, const void* b_t, const float* v, const float* v_t, void* out, void* out_t, void* out2,
                    void* out2_t, void* stream);
+
+/* Weight standardisation of every convolution of a net in one launch (csrc/ws.hip), as the engine runs it: the descriptors
+ * are built from `convs` (host memory) exactly as the engine builds them from its conv table, scale = gamma / sqrt(fan_in),
+ * fan_in = cin / groups * k * k.  theta (fp32): per conv the weight OIHW [cout, cin / groups, k, k], then the gain [cout].
+ * Packed buffers (dtype = MDD_DTYPE_F32 or _BF16 storage): conv i starts at the prefix sum of cout * k * k * cin_pad / groups
+ * in both layouts, wf [cout][k * k][cin_pad / groups] and wt [groups][cin_pad / groups][k * k][cout / groups]; lanes of the
+ * padded channels are never written.  cin_pad / groups and cout / groups must be whole 16-byte chunks of dtype.
+ *   mode 0  forward: writes wf and wt.  Tangent call (theta_t given): writes wf_t and wt_t, and wf / wt again when that
+ *           pair is given (both or neither)
+ *   mode 1  backward: dwf (fp32, wf layout; padded lanes are not read) -> gtheta in theta's layout: the gradient of the
+ *           weights and of the gains.  Tangent call (theta_t and dwf_t given): gtheta receives the tangent of that gradient
+ * The call returns after the launch has completed (the descriptor array lives for the call only). */
+typedef struct mdd_ws_conv {
+  int32_t cout, cin, k, groups, cin_pad;
+} mdd_ws_conv;
+int mdd_op_weight_std(int dtype, int mode, int nconv, const mdd_ws_conv* convs_host, float gamma, float eps,
+                      const float* theta, const float* theta_t, void* wf, void* wt, void* wf_t, void* wt_t,
+                      const float* dwf, const float* dwf_t, float* gtheta, void* stream);
+
+/* The pointwise, LayerNorm and row kernels of the text head (csrc/head.hip), fp32 [n, d] row-major.  A call is a TANGENT
+ * call when out_t is given: the `_t` operands of a, b, c (and out2_t) are then required, gamma_t / beta_t may be null (= 0),
+ * and ONLY the `_t` outputs are written (ops 0 - 2; op 3 see there).
+ *   op 0  gelu:      a = p -> out = g = GELU(p) (erf)
+ *   op 1  gelu_bwd:  a = p, b = rbar, c = gbar -> out = pbar = rbar + gbar * GELU'(p)
+ *   op 2  ln_fwd:    a = f, b = p, mask [n, d] or null (= 1) -> out2 = r = f * mask + p, out = y = LN(r) * gamma + beta.
+ *                    Tangent call: out2 holds the stashed r (read), out2_t = r_t, out_t = y_t
+ *   op 3  ln_bwd:    a = ybar, b = r, mask or null, gamma -> out = rbar, out2 = fbar = rbar * mask, dgamma [d], dbeta [d];
+ *                    stats: 4 n floats of scratch.  Tangent call: out_t = rbar_t, out2_t = fbar_t, and dgamma / dbeta
+ *                    receive the TANGENTS of the parameter gradients (as the engine's gradient vector does)
+ *   op 4  gather_rows:        out [n, d] = a[idx[r], :], idx int64 [n] or null (= the identity)
+ *   op 5  scatter_rows_axpy:  out[idx[r], :] += coef[0] * mul * a[r, :], coef a device scalar or null (= 1); the rows of idx
+ *                             are distinct
+ * eps is read by ops 2 and 3, mul by op 5. */
+int mdd_op_text_head(int op, int n, int d, float eps, float mul, const float* a, const float* a_t, const float* b,
+                     const float* b_t, const float* c, const float* c_t, const float* mask, const float* gamma,
+                     const float* gamma_t, const float* beta, const float* beta_t, const int64_t* idx, const float* coef,
+                     float* out, float* out_t, float* out2, float* out2_t, float* dgamma, float* dbeta, float* stats,
+                     void* stream);
 
 /* ---- synthetic-set evaluation: retrieval ranks.
  * Replaces the per-row host loops of reference epoch.py:140-156 (image->text: argsort of one similarity

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmdd_hip.so")
 
 DTYPE_F32, DTYPE_BF16, DTYPE_BF16X2, DTYPE_F32_BF16OPS = 0, 1, 2, 3
-ABI_VERSION = 10    # include/mdd_hip.h MDD_ABI_VERSION
+ABI_VERSION = 11    # include/mdd_hip.h MDD_ABI_VERSION
 
 
 class MddConfig(C.Structure):
@@ -74,6 +74,8 @@ SIGNATURES = {
     "mdd_op_mid_se": (_I, [_I] * 5 + [_F] + [_P] * 12),
     "mdd_op_linear": (_I, [_I] * 7 + [_F] + [_P] * 13),
     "mdd_op_pool_se": (_I, [_I] * 6 + [_F, _F] + [_P] * 11),
+    "mdd_op_weight_std": (_I, [_I, _I, _I, _P, _F, _F] + [_P] * 10),
+    "mdd_op_text_head": (_I, [_I, _I, _I, _F, _F] + [_P] * 21),
     "mdd_op_contrastive_workspace_floats": (_L, [_I, _I]),
     "mdd_op_contrastive": (_I, [_I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
     "mdd_retrieval_ranks": (_I, [_P] * 5 + [_I] * 3 + [C.c_float] + [_P] * 5),
@@ -101,6 +103,10 @@ class MddBgemmDesc(C.Structure):
                 ("c_row", C.c_int64), ("c_col", C.c_int64),
                 ("a_outer", C.c_int64), ("a_inner", C.c_int64), ("b_outer", C.c_int64), ("b_inner", C.c_int64),
                 ("c_outer", C.c_int64), ("c_inner", C.c_int64), ("alpha", C.c_float)]
+
+
+class MddWsConv(C.Structure):
+    _fields_ = [("cout", C.c_int32), ("cin", C.c_int32), ("k", C.c_int32), ("groups", C.c_int32), ("cin_pad", C.c_int32)]
 
 
 COMM_ID_BYTES = 128   # include/mdd_hip.h MDD_COMM_ID_BYTES

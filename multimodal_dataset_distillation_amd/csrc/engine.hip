@@ -44,6 +44,13 @@ int mdd_set_error_msg(int code, const char* msg) {
 #define CHECK_ARG(cond, msg) \
   do { if (!(cond)) return mdd_set_error_msg(2, "mdd: invalid argument: " msg); } while (0)
 #define POST_LAUNCH(what) HIP_CHECK_RET(hipGetLastError())
+// what launch_contrastive (csrc/head.hip) cannot take, refused before anything is launched
+#define CHECK_CONTRASTIVE(n, d)                                                                                        \
+  do {                                                                                                                 \
+    CHECK_ARG((int64_t)(n) * (n) <= 2147483647ll, "contrastive head: n * n overflows int");                            \
+    CHECK_ARG(contrastive_lds_bytes(n) <= 65536, "contrastive head: n needs more than the 64 KiB of LDS a workgroup may ask for (n <= 4092)"); \
+    CHECK_ARG((d) <= contrastive_max_d(), "contrastive head: d > 4096 (16 x 256 feature registers per row)");          \
+  } while (0)
 // inside Eng<AT> walkers: launch errors + latched stream-ordering / event errors
 #define POST_WALK()                                      \
   do {                                                   \
@@ -1793,6 +1800,7 @@ struct Eng : mdd_engine {
                   const float* scale_dev, float scale_const, float* loss, float* xb, float* yb,
                   float* sb, hipStream_t st) override {
     CHECK_ARG(base, "workspace not bound");
+    CHECK_CONTRASTIVE(N, feat);
     DevGuard guard(device_id);
     LossWork w = loss_work_carve(lossw, N, feat);
     if (!T) launch_contrastive(w, loss, xb, yb, sb, nullptr, nullptr, nullptr, x, y, nullptr,
@@ -2048,6 +2056,7 @@ int mdd_op_contrastive(int n, int d, const float* x, const float* y, const float
   CHECK_ARG(n > 0 && d > 0 && x && y && work && xbar && ybar && sbar, "null pointer / empty problem");
   CHECK_ARG((xd == nullptr) == (yd == nullptr), "x_dot and y_dot come together");
   CHECK_ARG(xd || loss, "loss output is null");
+  CHECK_CONTRASTIVE(n, d);
   LossWork w = loss_work_carve(work, n, d);
   if (!xd) launch_contrastive(w, loss, xbar, ybar, sbar, nullptr, nullptr, nullptr, x, y, nullptr, nullptr,
                               scale_dev, scale_const, n, d, (hipStream_t)stream);
@@ -2296,6 +2305,114 @@ int mdd_op_pool_se(int dtype, int op, int n, int h, int w, int c, float ga, floa
   };
   if (dtype == MDD_DTYPE_F32) run((float*)nullptr); else run((bf16*)nullptr);
   POST_LAUNCH("op_pool_se");
+  return 0;
+}
+
+int mdd_op_weight_std(int dtype, int mode, int nconv, const mdd_ws_conv* convs, float gamma, float eps, const float* theta,
+                      const float* theta_t, void* wf, void* wt, void* wf_t, void* wt_t, const float* dwf,
+                      const float* dwf_t, float* gtheta, void* stream) {
+  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype must be MDD_DTYPE_F32 or MDD_DTYPE_BF16");
+  CHECK_ARG(mode == 0 || mode == 1, "mode must be 0 (forward) or 1 (backward)");
+  CHECK_ARG(nconv > 0 && convs && theta, "null pointer / empty problem");
+  const bool T = theta_t != nullptr;
+  if (mode == 0) {
+    CHECK_ARG(T ? (wf_t && wt_t && (wf != nullptr) == (wt != nullptr)) : (wf && wt && !wf_t && !wt_t),
+              "forward: wf and wt (tangent: wf_t and wt_t, the primal pair both or neither)");
+    CHECK_ARG(!dwf && !dwf_t && !gtheta, "forward takes no gradient operands");
+  } else {
+    CHECK_ARG(dwf && gtheta && T == (dwf_t != nullptr), "backward: dwf and gtheta (tangent: dwf_t with theta_t)");
+    CHECK_ARG(!wf && !wt && !wf_t && !wt_t, "backward takes no packed weights");
+  }
+  // the descriptors, as Eng::create builds them from its conv table
+  std::vector<WsDesc> descs;
+  int64_t off = 0, off_p = 0, row = 0, tile = 0;
+  const int tr = ws_tile_rows(), ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
+  for (int i = 0; i < nconv; ++i) {
+    const mdd_ws_conv& L = convs[i];
+    CHECK_ARG(L.cout > 0 && L.cin > 0 && L.k > 0 && L.groups > 0 && L.cin_pad >= L.cin, "conv geometry");
+    CHECK_ARG(L.cout % L.groups == 0 && L.cin % L.groups == 0 && L.cin_pad % L.groups == 0, "groups must divide the channel counts");
+    WsDesc d;
+    d.cout = L.cout; d.cin_g = L.cin / L.groups; d.ksq = L.k * L.k; d.groups = L.groups;
+    d.cin_pad_g = L.cin_pad / L.groups; d.cout_g = L.cout / L.groups;
+    CHECK_ARG(d.cin_pad_g >= d.cin_g, "cin_pad / groups must cover cin / groups");
+    d.off_w = off; off += (int64_t)L.cout * d.cin_g * d.ksq;
+    d.off_g = off; off += L.cout;
+    d.off_b = d.off_g;      // no bias in this layout; weight standardisation never reads it
+    d.off_wf = off_p; d.off_wt = off_p; off_p += (int64_t)L.cout * d.ksq * d.cin_pad_g;
+    d.scale = gamma / std::sqrt((float)(d.cin_g * d.ksq)); d.eps = eps;
+    d.row_start = (int)row; row += L.cout;
+    d.tile_start = (int)tile; tile += d.groups * ((d.cout_g + tr - 1) / tr);
+    CHECK_ARG(row <= 2147483647ll && tile <= 2147483647ll, "too many rows");
+    CHECK_ARG(d.cin_pad_g % ce == 0 && d.cout_g % ce == 0, "channel counts must be multiples of the 16-byte chunk");
+    descs.push_back(d);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  WsDesc* d_descs = nullptr;
+  HIP_CHECK_RET(hipMalloc((void**)&d_descs, descs.size() * sizeof(WsDesc)));
+  hipError_t e = hipMemcpy(d_descs, descs.data(), descs.size() * sizeof(WsDesc), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    if (mode == 1) launch_ws_backward(d_descs, nconv, (int)row, theta, theta_t, dwf, dwf_t, gtheta, st);
+    else if (dtype == MDD_DTYPE_F32)
+      launch_ws_forward<float>(d_descs, nconv, (int)row, (int)tile, theta, theta_t, (float*)wf, (float*)wt, (float*)wf_t,
+                               (float*)wt_t, st);
+    else
+      launch_ws_forward<bf16>(d_descs, nconv, (int)row, (int)tile, theta, theta_t, (bf16*)wf, (bf16*)wt, (bf16*)wf_t,
+                              (bf16*)wt_t, st);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);     // the descriptors are freed below
+  }
+  (void)hipFree(d_descs);
+  HIP_CHECK_RET(e);
+  return 0;
+}
+
+int mdd_op_text_head(int op, int n, int d, float eps, float mul, const float* a, const float* a_t, const float* b,
+                     const float* b_t, const float* c, const float* c_t, const float* mask, const float* gamma,
+                     const float* gamma_t, const float* beta, const float* beta_t, const int64_t* idx, const float* coef,
+                     float* out, float* out_t, float* out2, float* out2_t, float* dgamma, float* dbeta, float* stats,
+                     void* stream) {
+  CHECK_ARG(op >= 0 && op <= 5, "op must be 0 (gelu), 1 (gelu_bwd), 2 (ln_fwd), 3 (ln_bwd), 4 (gather_rows) or 5 (scatter_rows_axpy)");
+  CHECK_ARG(n > 0 && d > 0, "empty problem");
+  CHECK_ARG(a && out, "null pointer");
+  const bool T = out_t != nullptr;
+  CHECK_ARG(T == (a_t != nullptr), "tangent operands come together");
+  CHECK_ARG(op == 2 || op == 3 || !(mask || gamma || gamma_t || beta || beta_t || out2 || out2_t || dgamma || dbeta || stats),
+            "LayerNorm operands belong to ops 2 and 3");
+  CHECK_ARG(op >= 4 || !(idx || coef), "idx and coef belong to ops 4 and 5");
+  CHECK_ARG(T || !(b_t || c_t || gamma_t || beta_t || out2_t), "tangent operands without a tangent output");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nd = (int64_t)n * d;
+  switch (op) {
+    case 0:   // a = p -> out = g
+      CHECK_ARG(!b && !b_t && !c && !c_t, "gelu takes one operand");
+      launch_gelu(out, out_t, a, a_t, nd, st);
+      break;
+    case 1:   // a = p, b = rbar, c = gbar -> out = pbar = rbar + gbar * gelu'(p)
+      CHECK_ARG(b && c && T == (b_t != nullptr) && T == (c_t != nullptr), "gelu_bwd: p, rbar, gbar (tangent: all three)");
+      launch_gelu_bwd(out, out_t, b, b_t, c, c_t, a, a_t, nd, st);
+      break;
+    case 2:   // a = f, b = p -> out2 = r = f * mask + p, out = y = LN(r) * gamma + beta
+      CHECK_ARG(b && gamma && beta && out2 && !c && !c_t, "ln_fwd: f, p, gamma, beta, y, r");
+      CHECK_ARG(T == (b_t != nullptr) && T == (out2_t != nullptr), "ln_fwd tangent: f_t, p_t, y_t, r_t");
+      CHECK_ARG(!dgamma && !dbeta && !stats, "ln_fwd has no parameter gradients");
+      launch_ln_fwd(out, out_t, out2, out2_t, a, a_t, mask, b, b_t, gamma, gamma_t, beta, beta_t, n, d, eps, st);
+      break;
+    case 3:   // a = ybar, b = r -> out = rbar, out2 = fbar = rbar * mask, dgamma, dbeta (tangent: their tangents)
+      CHECK_ARG(b && gamma && out2 && dgamma && dbeta && stats && !c && !c_t && !beta && !beta_t,
+                "ln_bwd: ybar, r, gamma, rbar, fbar, dgamma, dbeta, stats [4 n]");
+      CHECK_ARG(T == (b_t != nullptr) && T == (out2_t != nullptr), "ln_bwd tangent: ybar_t, r_t, rbar_t, fbar_t");
+      launch_ln_bwd(out, out_t, out2, out2_t, dgamma, dbeta, stats, a, a_t, b, b_t, mask, gamma, gamma_t, n, d, eps, st);
+      break;
+    case 4:   // out [n, d] = a[idx]
+      CHECK_ARG(!T && !b && !c && !coef, "gather_rows: in, idx");
+      launch_gather_rows(out, a, idx, n, d, st);
+      break;
+    default:  // out[idx] += coef * mul * a [n, d]
+      CHECK_ARG(!T && !b && !c, "scatter_rows_axpy: in, idx, coef");
+      launch_scatter_rows_axpy(out, a, idx, coef, mul, n, d, st);
+      break;
+  }
+  POST_LAUNCH("op_text_head");
   return 0;
 }
 

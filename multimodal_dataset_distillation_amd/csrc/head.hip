@@ -353,6 +353,10 @@ void launch_ln_bwd(float* rbar, float* rbar_t, float* fbar, float* fbar_t, float
   }
 }
 
+// What the launch below can take: k_featgrad keeps FG_MAX features per thread of its 256 (columns past that would never be
+// written and the row dot would stop short), k_ce asks for contrastive_lds_bytes(n) of dynamic LDS.
+int contrastive_max_d() { return FG_MAX * 256; }
+int64_t contrastive_lds_bytes(int n) { return (4 * (int64_t)n + 16) * (int64_t)sizeof(float); }
 int64_t loss_work_floats(int n, int d) { return 4ll * n * d + 4ll * n + 4ll * n * n + 64; }
 LossWork loss_work_carve(float* b, int n, int d) {
   LossWork w;
@@ -369,7 +373,7 @@ void launch_contrastive(const LossWork& w, float* loss, float* xbar, float* ybar
   bool dual = x_t != nullptr;
   int64_t waves = (int64_t)n * n;
   int lg = (int)((waves + 3) / 4);
-  size_t shm = (4 * n + 16) * sizeof(float);
+  size_t shm = (size_t)contrastive_lds_bytes(n);
   if (dual) {
     k_rownorm<Dual><<<2 * n, 256, 0, st>>>(w, x, y, x_t, y_t, n, d);
     k_logits<Dual><<<lg, 256, 0, st>>>(w, n, d);

@@ -310,6 +310,10 @@ struct LossWork {  // device scratch, sized by loss_work_floats(n, d)
   float* rny_t; float* G; float* G_t; float* Gb; float* Gb_t;
 };
 int64_t loss_work_floats(int n, int d);
+// limits of launch_contrastive: the callers refuse d > contrastive_max_d(), an n whose contrastive_lds_bytes(n) exceeds the
+// 64 KiB a workgroup may ask for, and an n whose n * n does not fit an int
+int contrastive_max_d();
+int64_t contrastive_lds_bytes(int n);
 LossWork loss_work_carve(float* base, int n, int d);
 void launch_contrastive(const LossWork& w, float* loss, float* xbar, float* ybar, float* sbar,
                         float* xbar_t, float* ybar_t, float* sbar_t, const float* x,

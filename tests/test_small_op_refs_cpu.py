@@ -221,7 +221,8 @@ def test_avgpool_inputs_expose_a_window_divided_by_four(n, h, w, c, dtype):
 
 
 def test_entry_points_reject_bad_arguments_before_any_launch():
-    """mdd_op_linear / mdd_op_pool_se validate on the host: none of these calls reaches a kernel (no GPU needed)."""
+    """mdd_op_linear / mdd_op_pool_se / mdd_op_weight_std / mdd_op_text_head / mdd_op_contrastive validate on the host:
+    none of these calls reaches a kernel (no GPU needed)."""
     import ctypes as C
     import os
     from multimodal_dataset_distillation_amd import _lib, build_ext
@@ -244,3 +245,36 @@ def test_entry_points_reject_bad_arguments_before_any_launch():
     assert pool(0, 7, 8, a_t=p) == 2                            # the average pool has no tangent form
     assert pool(0, 1, 8, a_t=p) == 2 and pool(0, 1, 8, out_t=p) == 2    # tangent operands come together
     assert pool(0, 3, 8, v=None) == 2
+    # weight standardisation: dtype, mode, geometry, which buffers belong to which mode, whole 16-byte chunks
+    err = lambda: lib.mdd_last_error()
+    convs = lambda *rows: (_lib.MddWsConv * len(rows))(*[_lib.MddWsConv(*r) for r in rows])
+    ok = convs((16, 3, 3, 1, 8))
+    ws = lambda dtype=0, mode=0, n=1, cv=ok, th=p, th_t=None, wf=p, wt=p, wf_t=None, wt_t=None, dwf=None, dwf_t=None, g=None: \
+        lib.mdd_op_weight_std(dtype, mode, n, cv, 1.7, 1e-5, th, th_t, wf, wt, wf_t, wt_t, dwf, dwf_t, g, None)
+    assert ws(dtype=2) == 2 and b"invalid argument" in err() and ws(mode=2) == 2 and ws(n=0) == 2 and ws(th=None) == 2
+    assert ws(wt=None) == 2 and ws(wf_t=p) == 2 and ws(dwf=p) == 2 and ws(g=p) == 2
+    assert ws(th_t=p) == 2 and ws(th_t=p, wf_t=p, wt_t=p, wt=None) == 2       # tangent: wf_t and wt_t; wf / wt both or neither
+    assert ws(mode=1) == 2 and ws(mode=1, wf=None, wt=None, dwf=p) == 2 and ws(mode=1, wf=None, wt=None, dwf=p, g=p, dwf_t=p) == 2
+    assert ws(mode=1, dwf=p, g=p) == 2                                          # backward takes no packed weights
+    assert ws(cv=convs((16, 3, 3, 1, 2))) == 2 and ws(cv=convs((16, 4, 3, 3, 9))) == 2 and ws(cv=convs((0, 3, 3, 1, 8))) == 2
+    assert ws(cv=convs((16, 3, 3, 1, 6))) == 2 and b"16-byte chunk" in err()   # cin_pad: whole chunks
+    assert ws(dtype=1, cv=convs((12, 8, 3, 1, 8))) == 2 and ws(n=2, cv=convs((16, 3, 3, 1, 8), (16, 8, 1, 1, 9))) == 2
+    # text head: op range, tangent operands together, operands that belong to other ops
+    th = lambda op, a=p, a_t=None, b=None, b_t=None, c=None, c_t=None, mask=None, gamma=None, gamma_t=None, beta=None, \
+        beta_t=None, idx=None, coef=None, out=p, out_t=None, out2=None, out2_t=None, dg=None, db=None, stats=None, n=2, d=8: \
+        lib.mdd_op_text_head(op, n, d, 1e-5, 1.0, a, a_t, b, b_t, c, c_t, mask, gamma, gamma_t, beta, beta_t, idx, coef, out,
+                             out_t, out2, out2_t, dg, db, stats, None)
+    assert th(6) == 2 and b"invalid argument" in err() and th(-1) == 2 and th(0, n=0) == 2 and th(0, a=None) == 2
+    assert th(0, out_t=p) == 2 and th(0, a_t=p) == 2 and th(0, b=p) == 2 and th(0, gamma=p) == 2 and th(0, idx=p) == 2
+    assert th(1) == 2 and th(1, b=p, c=p, a_t=p, out_t=p) == 2 and th(1, b=p, c=p, b_t=p) == 2
+    assert th(2, b=p, gamma=p, beta=p) == 2 and th(2, b=p, gamma=p, beta=p, out2=p, dg=p) == 2
+    assert th(2, b=p, gamma=p, beta=p, out2=p, a_t=p, out_t=p, b_t=p) == 2      # the tangent needs r_t
+    assert th(2, b=p, gamma=p, beta=p, out2=p, gamma_t=p) == 2                  # a tangent operand in a primal call
+    assert th(3, b=p, gamma=p, out2=p, dg=p, db=p) == 2 and th(3, b=p, gamma=p, out2=p, dg=p, db=p, stats=p, beta=p) == 2
+    assert th(4, a_t=p, out_t=p) == 2 and th(4, coef=p) == 2 and th(5, b=p) == 2 and th(4, mask=p) == 2
+    # contrastive head: what its kernels cannot take (d > 4096, the LDS request of n, n * n past int)
+    con = lambda n, d: lib.mdd_op_contrastive(n, d, p, p, None, None, None, 0.7, p, p, p, p, p, None)
+    assert con(4, 4097) == 2 and b"d > 4096" in err()
+    assert con(4093, 8) == 2 and b"64 KiB" in err()
+    assert con(46341, 8) == 2 and b"overflows int" in err()
+    assert con(0, 8) == 2 and con(4, 0) == 2
