@@ -67,9 +67,10 @@ typedef struct mdd_config {
 const char* mdd_last_error(void);
 /* ABI version of this header: 2 = round 2 (mdd_config.keep_steps, MDD_DTYPE_BF16X2 / _F32_BF16OPS,
  * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se; 9 = + mdd_set_se_fused; 10 = + mdd_op_linear, mdd_op_pool_se; 11 = + mdd_op_weight_std, mdd_op_text_head,
- * mdd_op_contrastive refuses what its kernels cannot take.  A binding built against another version
- * must refuse to load. */
-#define MDD_ABI_VERSION 11
+ * mdd_op_contrastive refuses what its kernels cannot take; 12 = + mdd_op_image_edge, mdd_op_vit_glue, mdd_op_lin_pack,
+ * mdd_op_resid, mdd_flat_dot / _scale_out / _sub_inplace / _lambda_init / _match_finalize / _d2f / _accum_f2d.  A binding
+ * built against another version must refuse to load. */
+#define MDD_ABI_VERSION 12
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
  * pipelined kernels; 0 routes them to the general kernels instead (process-wide; returns the previous setting).  For the
@@ -171,6 +172,22 @@ int mdd_flat_sgd_momentum(float* p_dev, const float* g_dev, float* buf_dev, floa
 int mdd_flat_sgd_momentum_guarded(float* p_dev, const float* g_dev, float* buf_dev, float lr,
                                   float mom, int first, int64_t n, const float* skip_flag_dev,
                                   void* stream);
+
+/* the reverse sweep's kernels over the same streams (the vector kernels move float4: 16-byte aligned pointers) */
+int mdd_flat_dot(const float* a_dev, const float* b_dev, double* out_dev, double sign, int64_t n,
+                 void* stream);                                /* out[0] += sign * <a, b>, accumulated in double */
+int mdd_flat_scale_out(float* y_dev, const float* x_dev, const float* coef_dev, float mul, int64_t n,
+                       void* stream);                          /* y = coef[0] * mul * x; coef a device scalar or NULL (= 1) */
+int mdd_flat_sub_inplace(float* y_dev, const float* x_dev, int64_t n, void* stream);       /* y -= x */
+/* lam = (float)(2 / dist0[0]) * (thK - tgt): d grand_loss / d theta_K (distill.py:588-597), dist0 a device double */
+int mdd_flat_lambda_init(float* lam_dev, const float* thK_dev, const float* tgt_dev, const double* dist0_dev, int64_t n,
+                         void* stream);
+/* s4 = {img_numer, img_denom, txt_numer, txt_denom} (double) -> out3 = {s0/s1 + s2/s3, s0/s1, s2/s3} (distill.py:596-598) */
+int mdd_flat_match_finalize(const double* s4_dev, float* out3_dev, void* stream);
+/* the scalar hand-overs: out[i] = (accum ? out[i] : 0) + (float)(in[i] * mul) for i < n, 1 <= n <= 64 (one wave; out is
+ * not read when accum == 0);  out[0] += sign * (double)in[0] */
+int mdd_flat_d2f(float* out_dev, const double* in_dev, float mul, int accum, int n, void* stream);
+int mdd_flat_accum_f2d(double* out_dev, const float* in_dev, double sign, void* stream);
 
 /* ---- one whole outer iteration (reference distill.py:509-606) */
 typedef struct mdd_iter_args {
@@ -321,6 +338,68 @@ int mdd_op_text_head(int op, int n, int d, float eps, float mul, const float* a,
                      const float* gamma_t, const float* beta, const float* beta_t, const int64_t* idx, const float* coef,
                      float* out, float* out_t, float* out2, float* out2_t, float* dgamma, float* dbeta, float* stats,
                      void* stream);
+
+/* The kernels at the two ends of every image pass: image_syn -> the first activation tensor, and the first layer's data
+ * gradient -> grad_image_syn (csrc/elementwise.hip, csrc/vit.hip, csrc/nfres.hip).  image / dimage are fp32 NCHW
+ * [nq, 3, h, w]; idx int64 [n] names the row of image / dimage that sample r reads / adds to, or is null (= the identity);
+ * activations are in the storage type (dtype = MDD_DTYPE_F32 or _BF16).  The accumulating ops add
+ * coef[0] * mul * (...) into dimage[idx[r]] (coef a device scalar or null = 1) WITHOUT atomics: the rows of idx must be
+ * distinct, as the engine's are within a step; rows of dimage that idx does not name are not touched.  Operands an op
+ * does not list must be null, parameters it does not list 0.
+ *   op 0  gather:    image -> out NHWC [n, h, w, c]; c = cpad >= 3 (the engine passes 8), channels 3 .. c - 1 are written +0
+ *   op 1  scatter:   a = x0bar [n, h, w, c] -> dimage[idx[r], ch, y, x] += coef * mul * x0bar[r, y, x, ch], ch < 3 (channels
+ *                    3 .. c - 1 are not read)
+ *   op 2  stem dgrad: the data gradient of Conv2d(3, cout, 3, stride 2, padding 1) straight into dimage: h = w = s,
+ *                    c = cout, a = dy1 [n, s/2, s/2, cout], wt1 = the packed data-gradient weight [8][9][cout] in the storage
+ *                    type (input channels 3 .. 7 are not read), optionally a2 = dy2, wt2 (the tangent pass: both or neither):
+ *                    dimage[idx[r]] += coef * mul * (dgrad(dy1, wt1) + dgrad(dy2, wt2)).  "invalid argument" when the
+ *                    kernel does not take the shape (s % 8 != 0, cout not 8 or 16: the engine then runs the implicit-GEMM data
+ *                    gradient and op 1)
+ *   op 3  patchify:  image -> out [n * (s/p)^2, 3 p p], h = w = s, c = 3, k = p, s % p == 0; row (r, py, px), column
+ *                    ch * p * p + dy * p + dx = image[idx[r], ch, py * p + dy, px * p + dx]
+ *   op 4  unpatchify_accum: a = colsbar in that layout -> dimage += coef * mul * (the same map backwards)
+ *   op 5  im2col:    a = NHWC [n, h, w, c] (c = cpad, whole 16-byte chunks) -> out col [n * ho * wo, k * k * c], column
+ *                    (ty * k + tx) * c + ch = a[r, oy * stride - pad + ty, ox * stride - pad + tx, ch], +0 outside the image;
+ *                    ho = (h + 2 pad - k) / stride + 1, the same for wo.  No idx. */
+int mdd_op_image_edge(int dtype, int op, int n, int h, int w, int c, int k, int stride, int pad, float mul,
+                      const float* image, const int64_t* idx, const float* coef, const void* a, const void* wt1,
+                      const void* a2, const void* wt2, void* out, float* dimage, void* stream);
+
+/* The ViT's token glue (csrc/vit.hip).  Activations [n, tok, dim] in the storage type, cls [dim] / pos [tok, dim] and
+ * dcls / dpos fp32.  A call is a TANGENT call when a_t is given (ops 0, 1, 4 only): every `_t` operand of the op is then
+ * required and ONLY the `_t` outputs are written (op 1: see there).  Operands an op does not list must be null.
+ *   op 0  embed:       a = pe [n, tok - 1, dim], cls, pos -> out = x0: x0[r, 0] = cls + pos[0], x0[r, 1 + p] = pe[r, p] + pos[1 + p]
+ *                      (tangent: a_t, cls_t, pos_t -> out_t)
+ *   op 1  embed_bwd:   a = xbar [n, tok, dim] -> out = pebar [n, tok - 1, dim] = xbar[:, 1:], dpos [tok, dim] = sum_r xbar[r],
+ *                      dcls [dim] = sum_r xbar[r, 0].  dpos and dcls are OVERWRITTEN (they are slices of the flat gradient).
+ *                      Tangent call (a_t -> out_t; out may be null): dpos / dcls receive the sums of xbar_t, the TANGENTS of
+ *                      the parameter gradients
+ *   op 2  cls_gather:  a = x [n, tok, dim] -> out [n, dim] = x[:, 0]
+ *   op 3  cls_scatter: a = in [n, dim] -> out = xbar [n, tok, dim]: xbar[:, 0] = in, every other row written +0
+ *   op 4  add2:        out = a + b over n * tok * dim elements, a multiple of the 16-byte chunk (tangent: a_t, b_t -> out_t)
+ *   op 5  act_to_f32:  a (storage type) -> out fp32, n * tok * dim elements ;  op 6  f32_to_act: a fp32 -> out (storage type) */
+int mdd_op_vit_glue(int dtype, int op, int n, int tok, int dim, const void* a, const void* a_t, const void* b, const void* b_t,
+                    const float* cls, const float* cls_t, const float* pos, const float* pos_t, void* out, void* out_t,
+                    float* dcls, float* dpos, void* stream);
+
+/* The packed operands of every linear of a ViT in one launch (csrc/vit.hip k_lin_pack_all), as the engine runs it: the
+ * descriptors are built from `shapes` (host memory: nlin pairs {out, in}) exactly as the engine builds them from its table
+ * of linears.  theta (fp32): per linear the weight [out][in], then the bias [out], which is never read.  Packed buffers
+ * (storage type): linear i starts at the prefix sum of out * in in both, wf = W as stored [out][in], wt = W^T [in][out];
+ * every element of both is written.  Tangent call (theta_t given): wf_t and wt_t are required and receive the same packing
+ * of theta_t, and wf / wt are WRITTEN AGAIN from theta (all four buffers are outputs).
+ * The call returns after the launch has completed (the descriptor array lives for the call only). */
+int mdd_op_lin_pack(int dtype, int nlin, const int32_t* shapes_host, const float* theta, const float* theta_t, void* wf,
+                    void* wt, void* wf_t, void* wt_t, void* stream);
+
+/* The residual sum of a block without squeeze-excite (csrc/nfres.hip, csrc/nfreg.hip) over `elems` elements of the storage
+ * type, a multiple of the 16-byte chunk:  xo = x' = alpha * c3 + sc,  ao = beta * act(x') (ao may be null).
+ *   op 0  act = ReLU (NF-ResNet) ;  op 1  act = SiLU (NF-RegNet)
+ *         Tangent call (c3_t given: sc_t and xo_t required): ONLY xo_t and, when ao_t is given, ao_t are written (ao is then
+ *         the stashed primal; ReLU's tangent is beta * [x' > 0] * x'_t with x' recomputed from c3 and sc)
+ *   op 2  xo = alpha * c3 (no other operand) */
+int mdd_op_resid(int dtype, int op, int64_t elems, float alpha, float beta, const void* c3, const void* c3_t, const void* sc,
+                 const void* sc_t, void* xo, void* xo_t, void* ao, void* ao_t, void* stream);
 
 /* ---- synthetic-set evaluation: retrieval ranks.
  * Replaces the per-row host loops of reference epoch.py:140-156 (image->text: argsort of one similarity

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmdd_hip.so")
 
 DTYPE_F32, DTYPE_BF16, DTYPE_BF16X2, DTYPE_F32_BF16OPS = 0, 1, 2, 3
-ABI_VERSION = 11    # include/mdd_hip.h MDD_ABI_VERSION
+ABI_VERSION = 12    # include/mdd_hip.h MDD_ABI_VERSION
 
 
 class MddConfig(C.Structure):
@@ -59,6 +59,13 @@ SIGNATURES = {
     "mdd_flat_sqdist": (_I, [_P, _P, _P, _L, _P]),
     "mdd_flat_sgd_momentum": (_I, [_P, _P, _P, _F, _F, _I, _L, _P]),
     "mdd_flat_sgd_momentum_guarded": (_I, [_P, _P, _P, _F, _F, _I, _L, _P, _P]),
+    "mdd_flat_dot": (_I, [_P, _P, _P, C.c_double, _L, _P]),
+    "mdd_flat_scale_out": (_I, [_P, _P, _P, _F, _L, _P]),
+    "mdd_flat_sub_inplace": (_I, [_P, _P, _L, _P]),
+    "mdd_flat_lambda_init": (_I, [_P, _P, _P, _P, _L, _P]),
+    "mdd_flat_match_finalize": (_I, [_P, _P, _P]),
+    "mdd_flat_d2f": (_I, [_P, _P, _F, _I, _I, _P]),
+    "mdd_flat_accum_f2d": (_I, [_P, _P, C.c_double, _P]),
     "mdd_engine_profile": (_I, [_P, _I]),
     "mdd_engine_set_pass_precision": (_I, [_P, _I, _I, _I, _I]),
     "mdd_engine_profile_read": (_I, [_P, _I, C.POINTER(C.c_double)]),
@@ -76,6 +83,10 @@ SIGNATURES = {
     "mdd_op_pool_se": (_I, [_I] * 6 + [_F, _F] + [_P] * 11),
     "mdd_op_weight_std": (_I, [_I, _I, _I, _P, _F, _F] + [_P] * 10),
     "mdd_op_text_head": (_I, [_I, _I, _I, _F, _F] + [_P] * 21),
+    "mdd_op_image_edge": (_I, [_I] * 9 + [_F] + [_P] * 10),
+    "mdd_op_vit_glue": (_I, [_I] * 5 + [_P] * 13),
+    "mdd_op_lin_pack": (_I, [_I, _I] + [_P] * 8),
+    "mdd_op_resid": (_I, [_I, _I, _L, _F, _F] + [_P] * 9),
     "mdd_op_contrastive_workspace_floats": (_L, [_I, _I]),
     "mdd_op_contrastive": (_I, [_I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
     "mdd_retrieval_ranks": (_I, [_P] * 5 + [_I] * 3 + [C.c_float] + [_P] * 5),

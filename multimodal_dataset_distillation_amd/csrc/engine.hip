@@ -2438,4 +2438,189 @@ int mdd_nearest_neighbor(const float* query, const float* bank, int n_query, int
   return 0;
 }
 
+// ---- the kernels at the edges of every pass (parity tests): argument checks, then the engine's own launchers
+#define CHECK_STORAGE(dtype) CHECK_ARG((dtype) == MDD_DTYPE_F32 || (dtype) == MDD_DTYPE_BF16, "dtype must be MDD_DTYPE_F32 or MDD_DTYPE_BF16")
+
+int mdd_op_image_edge(int dtype, int op, int n, int h, int w, int c, int k, int stride, int pad, float mul,
+                      const float* image, const int64_t* idx, const float* coef, const void* a, const void* wt1,
+                      const void* a2, const void* wt2, void* out, float* dimage, void* stream) {
+  CHECK_STORAGE(dtype);
+  CHECK_ARG(op >= 0 && op <= 5, "op must be 0 (gather), 1 (scatter), 2 (stem dgrad), 3 (patchify), 4 (unpatchify_accum) or 5 (im2col)");
+  CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0, "empty problem");
+  CHECK_ARG((int64_t)n * h * w <= 2147483647ll / 64, "problem too large");
+  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
+  const bool reads_image = op == 0 || op == 3, accumulates = op == 1 || op == 2 || op == 4;
+  CHECK_ARG(reads_image ? (image && out && !a && !dimage) : (a && !image), "gather / patchify: image -> out; the others read a");
+  CHECK_ARG(accumulates ? (dimage && !out) : (out && !dimage && !coef), "scatter / stem dgrad / unpatchify_accum: dimage (+ coef); the others: out");
+  CHECK_ARG(op != 5 || !idx, "im2col takes no idx");
+  CHECK_ARG(op == 2 ? (wt1 && (a2 == nullptr) == (wt2 == nullptr)) : (!wt1 && !a2 && !wt2), "stem dgrad: dy1, wt1 and the second pair whole or not at all; the others take no weights");
+  CHECK_ARG(op == 3 || op == 4 || op == 5 || (k == 0 && stride == 0 && pad == 0), "k, stride, pad belong to patchify / unpatchify_accum (k) and im2col");
+  if (op <= 1) CHECK_ARG(c >= 3, "cpad must hold the 3 image channels");
+  if (op == 2) CHECK_ARG(h == w, "stem dgrad: square images");
+  if (op == 3 || op == 4) CHECK_ARG(h == w && k > 0 && stride == 0 && pad == 0 && h % k == 0 && c == 3, "patches: square images, s % p == 0, c = 3");
+  if (op == 5) {
+    CHECK_ARG(k > 0 && stride > 0 && pad >= 0 && h + 2 * pad >= k && w + 2 * pad >= k, "im2col: conv geometry");
+    CHECK_ARG(c % ce == 0, "im2col: cpad must be a multiple of the 16-byte chunk");
+    CHECK_ARG((int64_t)((w + 2 * pad - k) / stride + 1) * k * k * (c / ce) <= 2147483647ll, "im2col: row too long");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  bool taken = true;
+  auto run = [&](auto* tag) {
+    using AT = std::remove_pointer_t<decltype(tag)>;
+    switch (op) {
+      case 0: launch_img_gather_nhwc<AT>((AT*)out, image, idx, n, 3, h, w, c, st); break;
+      case 1: launch_img_scatter_grad<AT>(dimage, (const AT*)a, idx, coef, mul, n, 3, h, w, c, st); break;
+      case 2: taken = launch_stem_dgrad_image<AT>(dimage, (const AT*)a, (const AT*)wt1, (const AT*)a2, (const AT*)wt2, idx, coef, mul, n, h, c, 8, st); break;
+      case 3: launch_patchify<AT>((AT*)out, image, idx, n, h, k, st); break;
+      case 4: launch_unpatchify_accum<AT>(dimage, (const AT*)a, idx, coef, mul, n, h, k, st); break;
+      default: launch_im2col<AT>((AT*)out, (const AT*)a, n, h, w, c, k, stride, pad, (h + 2 * pad - k) / stride + 1, (w + 2 * pad - k) / stride + 1, st); break;
+    }
+  };
+  if (dtype == MDD_DTYPE_F32) run((float*)nullptr); else run((bf16*)nullptr);
+  CHECK_ARG(taken, "stem dgrad: s must be a multiple of 8 and cout 8 or 16");
+  POST_LAUNCH("op_image_edge");
+  return 0;
+}
+
+int mdd_op_vit_glue(int dtype, int op, int n, int tok, int dim, const void* a, const void* a_t, const void* b, const void* b_t,
+                    const float* cls, const float* cls_t, const float* pos, const float* pos_t, void* out, void* out_t,
+                    float* dcls, float* dpos, void* stream) {
+  CHECK_STORAGE(dtype);
+  CHECK_ARG(op >= 0 && op <= 6, "op must be 0 (embed), 1 (embed_bwd), 2 (cls_gather), 3 (cls_scatter), 4 (add2), 5 (act_to_f32) or 6 (f32_to_act)");
+  CHECK_ARG(n > 0 && tok > 0 && dim > 0, "empty problem");
+  CHECK_ARG(a, "null pointer");
+  const bool T = a_t != nullptr;
+  CHECK_ARG(T == (out_t != nullptr), "tangent operands come together");
+  CHECK_ARG(T || out, "null output");
+  CHECK_ARG(!T || op == 0 || op == 1 || op == 4, "only embed, embed_bwd and add2 have a tangent form");
+  CHECK_ARG(op == 0 ? (cls && pos && T == (cls_t != nullptr) && T == (pos_t != nullptr)) : (!cls && !cls_t && !pos && !pos_t),
+            "embed: cls and pos (tangent: cls_t and pos_t); the others take neither");
+  CHECK_ARG(op == 1 ? (dcls && dpos) : (!dcls && !dpos), "embed_bwd: dcls and dpos; the others take neither");
+  CHECK_ARG(op == 4 ? (b && T == (b_t != nullptr)) : (!b && !b_t), "add2: b (tangent: b_t); the others take one operand");
+  CHECK_ARG(op > 1 || tok >= 2, "embed: the class token and at least one patch");
+  const int64_t elems = (int64_t)n * tok * dim;
+  CHECK_ARG(op != 4 || elems % (dtype == MDD_DTYPE_F32 ? 4 : 8) == 0, "add2: n * tok * dim must be a multiple of the 16-byte chunk");
+  hipStream_t st = (hipStream_t)stream;
+  auto run = [&](auto* tag) {
+    using AT = std::remove_pointer_t<decltype(tag)>;
+    const AT *A = (const AT*)a, *A_t = (const AT*)a_t;
+    switch (op) {
+      case 0: launch_vit_embed<AT>((AT*)out, (AT*)out_t, A, A_t, cls, cls_t, pos, pos_t, n, tok, dim, st); break;
+      case 1: launch_vit_embed_bwd<AT>(A, A_t, (AT*)out, (AT*)out_t, dcls, dpos, n, tok, dim, st); break;
+      case 2: launch_cls_gather<AT>((AT*)out, A, n, tok, dim, st); break;
+      case 3: launch_cls_scatter<AT>((AT*)out, A, n, tok, dim, st); break;
+      case 4: launch_add2<AT>((AT*)out, (AT*)out_t, A, A_t, (const AT*)b, (const AT*)b_t, elems, st); break;
+      case 5: launch_act_to_f32<AT>((float*)out, A, elems, st); break;
+      default: launch_f32_to_act<AT>((AT*)out, (const float*)a, elems, st); break;
+    }
+  };
+  if (dtype == MDD_DTYPE_F32) run((float*)nullptr); else run((bf16*)nullptr);
+  POST_LAUNCH("op_vit_glue");
+  return 0;
+}
+
+int mdd_op_lin_pack(int dtype, int nlin, const int32_t* shapes, const float* theta, const float* theta_t, void* wf, void* wt,
+                    void* wf_t, void* wt_t, void* stream) {
+  CHECK_STORAGE(dtype);
+  CHECK_ARG(nlin > 0 && shapes && theta && wf && wt, "null pointer / empty problem");
+  CHECK_ARG(theta_t ? (wf_t && wt_t) : (!wf_t && !wt_t), "wf_t and wt_t come with theta_t");
+  // the descriptors, as Eng::create builds them from its table of linears
+  std::vector<LinPackDesc> lpd;
+  int64_t off = 0, off_p = 0, tiles = 0;
+  for (int i = 0; i < nlin; ++i) {
+    const int out = shapes[2 * i], in = shapes[2 * i + 1];
+    CHECK_ARG(out > 0 && in > 0, "linear geometry");
+    LinPackDesc d; d.off_w = off; d.off_p = off_p; d.out = out; d.in = in; d.tile_start = (int)tiles; d.pad_ = 0;
+    off += (int64_t)out * in + out; off_p += (int64_t)out * in;
+    tiles += (int64_t)((in + 63) / 64) * ((out + 63) / 64);      // k_lin_pack_all: 64 x 64 tiles
+    CHECK_ARG(tiles <= 2147483647ll, "too many tiles");
+    lpd.push_back(d);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  LinPackDesc* d_lpd = nullptr;
+  HIP_CHECK_RET(hipMalloc((void**)&d_lpd, lpd.size() * sizeof(LinPackDesc)));
+  hipError_t e = hipMemcpy(d_lpd, lpd.data(), lpd.size() * sizeof(LinPackDesc), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    if (dtype == MDD_DTYPE_F32)
+      launch_lin_pack_all<float>(d_lpd, nlin, (int)tiles, theta, theta_t, (float*)wf, (float*)wt, (float*)wf_t, (float*)wt_t, st);
+    else
+      launch_lin_pack_all<bf16>(d_lpd, nlin, (int)tiles, theta, theta_t, (bf16*)wf, (bf16*)wt, (bf16*)wf_t, (bf16*)wt_t, st);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);     // the descriptors are freed below
+  }
+  (void)hipFree(d_lpd);
+  HIP_CHECK_RET(e);
+  return 0;
+}
+
+int mdd_op_resid(int dtype, int op, int64_t elems, float alpha, float beta, const void* c3, const void* c3_t, const void* sc,
+                 const void* sc_t, void* xo, void* xo_t, void* ao, void* ao_t, void* stream) {
+  CHECK_STORAGE(dtype);
+  CHECK_ARG(op >= 0 && op <= 2, "op must be 0 (ReLU), 1 (SiLU) or 2 (scale)");
+  CHECK_ARG(elems > 0 && elems % (dtype == MDD_DTYPE_F32 ? 4 : 8) == 0, "elems must be a positive multiple of the 16-byte chunk");
+  CHECK_ARG(c3 && xo, "null pointer");
+  const bool T = c3_t != nullptr;
+  if (op == 2) CHECK_ARG(!T && !sc && !sc_t && !xo_t && !ao && !ao_t, "scale: in, out");
+  else {
+    CHECK_ARG(sc && T == (sc_t != nullptr) && T == (xo_t != nullptr), "tangent operands come together");
+    CHECK_ARG(T ? (!ao_t || ao) : !ao_t, "ao_t belongs to the tangent form, with the stashed ao");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  auto run = [&](auto* tag) {
+    using AT = std::remove_pointer_t<decltype(tag)>;
+    // the tangent form stores through ao_t alone: without it there is no activation output at all
+    AT* AO = (AT*)(T && !ao_t ? nullptr : ao);
+    if (op == 0) launch_resid_relu<AT>((const AT*)c3, (const AT*)c3_t, (const AT*)sc, (const AT*)sc_t, (AT*)xo, (AT*)xo_t, AO, (AT*)ao_t, alpha, beta, elems, st);
+    else if (op == 1) launch_resid_silu<AT>((const AT*)c3, (const AT*)c3_t, (const AT*)sc, (const AT*)sc_t, (AT*)xo, (AT*)xo_t, AO, (AT*)ao_t, alpha, beta, elems, st);
+    else launch_scale_act<AT>((AT*)xo, (const AT*)c3, alpha, elems, st);
+  };
+  if (dtype == MDD_DTYPE_F32) run((float*)nullptr); else run((bf16*)nullptr);
+  POST_LAUNCH("op_resid");
+  return 0;
+}
+
+int mdd_flat_dot(const float* a, const float* b, double* out, double sign, int64_t n, void* stream) {
+  CHECK_ARG(a && b && out && n >= 0, "null pointer");
+  launch_dot(a, b, out, sign, n, (hipStream_t)stream);
+  POST_LAUNCH("dot");
+  return 0;
+}
+int mdd_flat_scale_out(float* y, const float* x, const float* coef, float mul, int64_t n, void* stream) {
+  CHECK_ARG(y && x && n >= 0, "null pointer");
+  launch_scale_out(y, x, coef, mul, n, (hipStream_t)stream);
+  POST_LAUNCH("scale_out");
+  return 0;
+}
+int mdd_flat_sub_inplace(float* y, const float* x, int64_t n, void* stream) {
+  CHECK_ARG(y && x && n >= 0, "null pointer");
+  launch_sub_inplace(y, x, n, (hipStream_t)stream);
+  POST_LAUNCH("sub_inplace");
+  return 0;
+}
+int mdd_flat_lambda_init(float* lam, const float* thK, const float* tgt, const double* dist0, int64_t n, void* stream) {
+  CHECK_ARG(lam && thK && tgt && dist0 && n >= 0, "null pointer");
+  launch_lambda_init(lam, thK, tgt, dist0, n, (hipStream_t)stream);
+  POST_LAUNCH("lambda_init");
+  return 0;
+}
+int mdd_flat_match_finalize(const double* s4, float* out3, void* stream) {
+  CHECK_ARG(s4 && out3, "null pointer");
+  launch_match_finalize(s4, out3, (hipStream_t)stream);
+  POST_LAUNCH("match_finalize");
+  return 0;
+}
+int mdd_flat_d2f(float* out, const double* in, float mul, int accum, int n, void* stream) {
+  CHECK_ARG(out && in, "null pointer");
+  CHECK_ARG(n >= 1 && n <= 64, "d2f hands over at most 64 scalars (one wave)");
+  launch_d2f(out, in, mul, accum, n, (hipStream_t)stream);
+  POST_LAUNCH("d2f");
+  return 0;
+}
+int mdd_flat_accum_f2d(double* out, const float* in, double sign, void* stream) {
+  CHECK_ARG(out && in, "null pointer");
+  launch_accum_f2d(out, in, sign, (hipStream_t)stream);
+  POST_LAUNCH("accum_f2d");
+  return 0;
+}
+
 }  // extern "C"

@@ -501,25 +501,6 @@ template <class AT> __global__ void k_act_to_f32(float* __restrict__ o, const AT
 template <class AT> __global__ void k_f32_to_act(AT* __restrict__ o, const float* __restrict__ a, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) o[i] = from_f<AT>(a[i]);
 }
-// packed operands of a linear W [out][in] (fp32 in theta): wf = W as stored (B operand of the forward contraction),
-// wt = W^T [in][out] (B operand of the data gradient); 32x32 tiles through LDS
-template <class AT>
-__global__ void k_lin_pack(AT* __restrict__ wf, AT* __restrict__ wt, const float* __restrict__ w, int out, int in) {
-  __shared__ float tile[32][33];
-  const int i0 = blockIdx.x * 32, o0 = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 256 threads: 8 rows per pass
-  for (int r = ty; r < 32; r += 8) {
-    const int o = o0 + r, i = i0 + tx;
-    float v = 0.f;
-    if (o < out && i < in) { v = w[(int64_t)o * in + i]; wf[(int64_t)o * in + i] = from_f<AT>(v); }
-    tile[r][tx] = v;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int i = i0 + r, o = o0 + tx;
-    if (o < out && i < in) wt[(int64_t)i * out + o] = from_f<AT>(tile[tx][r]);
-  }
-}
 
 // ------------------------------------------------------------------ the same contraction on the matrix cores (bf16 storage)
 // 64 x 64 output tile, four waves of 32 x 32 (v_mfma_f32_32x32x16_bf16), K-step 32.  Operands are staged through LDS
@@ -860,11 +841,9 @@ template <class AT> void launch_act_to_f32(float* o, const AT* a, int64_t n, hip
 template <class AT> void launch_f32_to_act(AT* o, const float* a, int64_t n, hipStream_t st) {
   k_f32_to_act<AT><<<vgrid(n), 256, 0, st>>>(o, a, n);
 }
-template <class AT> void launch_lin_pack(AT* wf, AT* wt, const float* w, int out, int in, hipStream_t st) {
-  k_lin_pack<AT><<<dim3((in + 31) / 32, (out + 31) / 32), 256, 0, st>>>(wf, wt, w, out, in);
-}
-// every linear of the network (and, with theta_t, its tangent) in ONE launch: block -> (layer, 32x32 tile) by the
-// layers' tile prefix sums
+// packed operands of every linear W [out][in] (fp32 in theta) of the network in ONE launch: wf = W as stored (B operand of
+// the forward contraction), wt = W^T [in][out] (B operand of the data gradient); with theta_t the tangents wf_t / wt_t as
+// well (the primal pair is then written again).  block -> (layer, 64 x 64 tile) by the layers' tile prefix sums
 template <class AT>
 __global__ __launch_bounds__(256) void k_lin_pack_all(const LinPackDesc* __restrict__ descs, int nd, const float* __restrict__ th,
                                                       const float* __restrict__ th_t, AT* __restrict__ wf, AT* __restrict__ wt,
@@ -940,7 +919,6 @@ void launch_lin_pack_all(const LinPackDesc* descs, int nd, int total_tiles, cons
   template void launch_cls_scatter<AT>(AT*, const AT*, int, int, int, hipStream_t);                               \
   template void launch_act_to_f32<AT>(float*, const AT*, int64_t, hipStream_t);                                   \
   template void launch_f32_to_act<AT>(AT*, const float*, int64_t, hipStream_t);                                   \
-  template void launch_lin_pack<AT>(AT*, AT*, const float*, int, int, hipStream_t);                               \
   template void launch_lin_pack_all<AT>(const LinPackDesc*, int, int, const float*, const float*, AT*, AT*, AT*, AT*, \
                                         hipStream_t);
 VIT_INST(float)
