@@ -68,9 +68,10 @@ const char* mdd_last_error(void);
 /* ABI version of this header: 2 = round 2 (mdd_config.keep_steps, MDD_DTYPE_BF16X2 / _F32_BF16OPS,
  * profile kind 4); 3 = + mdd_comm_* / mdd_allreduce_syn_grads; 4 = + the ViT building-block ops; 5 = + mdd_engine_set_pass_precision; 6 = + mdd_op_conv2d_wgrad2, mdd_set_pipe_kernels; 7 = + mdd_op_maxpool2d_3s2; 8 = + mdd_set_group8_kernels, mdd_op_mid_se; 9 = + mdd_set_se_fused; 10 = + mdd_op_linear, mdd_op_pool_se; 11 = + mdd_op_weight_std, mdd_op_text_head,
  * mdd_op_contrastive refuses what its kernels cannot take; 12 = + mdd_op_image_edge, mdd_op_vit_glue, mdd_op_lin_pack,
- * mdd_op_resid, mdd_flat_dot / _scale_out / _sub_inplace / _lambda_init / _match_finalize / _d2f / _accum_f2d.  A binding
- * built against another version must refuse to load. */
-#define MDD_ABI_VERSION 12
+ * mdd_op_resid, mdd_flat_dot / _scale_out / _sub_inplace / _lambda_init / _match_finalize / _d2f / _accum_f2d; 13 = +
+ * in-engine dropout masks (mdd_iter_args.drop_p / drop_iteration / drop_seed, mdd_txt_forward_rng, mdd_op_dropout_mask,
+ * mdd_sizeof_iter_args).  A binding built against another version must refuse to load. */
+#define MDD_ABI_VERSION 13
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
  * pipelined kernels; 0 routes them to the general kernels instead (process-wide; returns the previous setting).  For the
@@ -127,6 +128,23 @@ int mdd_img_tangent_backward(mdd_engine* e, int slot, const float* theta_dev,
 int mdd_txt_forward(mdd_engine* e, int slot, const float* theta_dev, const float* text_syn_dev,
                     const int64_t* idx_dev, const float* drop_mask_dev, float* feat_out_dev,
                     void* stream);
+/* The same pass with the dropout mask DRAWN BY THE ENGINE (reference networks.py:636,643: Dropout(p) in train mode).
+ * Nothing is stored: the slot remembers (p, seed, step, iteration, idx_dev) and mdd_txt_backward, mdd_txt_tangent_forward
+ * and mdd_txt_tangent_backward of that slot draw the same mask again, so idx_dev must stay valid until the last of them.
+ * The mask (normative; tests/dropout_refs.py restates it): Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53,
+ * 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85), key = (seed low word, seed high word), counter = (column / 4, sample,
+ * step, iteration), output word column % 4 belongs to `column`; sample = (uint32_t)idx_dev[row], or row when idx_dev is
+ * NULL (a shard that runs some rows of a minibatch draws exactly those rows of the unsharded mask); u = (word >> 8) *
+ * 2^-24, keep iff u >= p, mask = keep ? 1.0f / (1.0f - p) : 0.  p in [0, 1), 0 = no dropout; anything else (NaN too) is
+ * "invalid argument" before anything is launched.  The call keeps no state of its own: the same arguments give the same
+ * mask on any engine. */
+int mdd_txt_forward_rng(mdd_engine* e, int slot, const float* theta_dev, const float* text_syn_dev,
+                        const int64_t* idx_dev, float p, uint64_t seed, uint32_t step, uint32_t iteration,
+                        float* feat_out_dev, void* stream);
+/* That mask itself, [n, d] fp32 (to inspect it, or to inject it through drop_mask_dev / mdd_iter_args.drop_masks);
+ * idx_dev int64 [n] or NULL.  Same argument checks. */
+int mdd_op_dropout_mask(float p, uint64_t seed, uint32_t step, uint32_t iteration, int n, int d,
+                        const int64_t* idx_dev, float* out_dev, void* stream);
 int mdd_txt_backward(mdd_engine* e, int slot, const float* theta_dev, const float* feat_bar_dev,
                      float* gtheta_out_dev, float* dtext_accum_dev, const int64_t* idx_dev,
                      const float* coef_dev, float mul, int stash, void* stream);
@@ -208,7 +226,15 @@ typedef struct mdd_iter_args {
   float* grad_text_syn;      /* out                                                            */
   float* grad_lr;            /* out [2]: d/d lr_img, d/d lr_txt                                */
   float* losses;             /* out [3 + syn_steps]: grand, img, txt, contrastive per step     */
+  /* used when drop_masks == NULL and drop_p > 0: the engine draws step k's mask itself (mdd_txt_forward_rng with
+   * step = k, idx = perms + k * batch) in the forward, the inner gradient, both tangent passes and the recomputed
+   * steps of keep_steps.  drop_p outside [0, 1), or drop_masks together with drop_p > 0: "invalid argument" */
+  float drop_p;
+  uint32_t drop_iteration;   /* the outer iteration: counter word 3                            */
+  uint64_t drop_seed;
 } mdd_iter_args;
+/* sizeof(mdd_iter_args) as the library was built: a binding checks its own layout against it */
+size_t mdd_sizeof_iter_args(void);
 int mdd_unrolled_match(mdd_engine* e, const mdd_iter_args* a, void* stream);
 
 /* ---- per-kernel HIP-event timing of the contraction launches (bench.py roofline accounting).

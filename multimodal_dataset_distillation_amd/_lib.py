@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmdd_hip.so")
 
 DTYPE_F32, DTYPE_BF16, DTYPE_BF16X2, DTYPE_F32_BF16OPS = 0, 1, 2, 3
-ABI_VERSION = 12    # include/mdd_hip.h MDD_ABI_VERSION
+ABI_VERSION = 13    # include/mdd_hip.h MDD_ABI_VERSION
 
 
 class MddConfig(C.Structure):
@@ -26,7 +26,8 @@ class MddIterArgs(C.Structure):
                 ("drop_masks", C.c_void_p), ("syn_steps", C.c_int32),
                 ("use_lr_as_scale", C.c_int32), ("logit_scale_const", C.c_float),
                 ("grad_image_syn", C.c_void_p), ("grad_text_syn", C.c_void_p),
-                ("grad_lr", C.c_void_p), ("losses", C.c_void_p)]
+                ("grad_lr", C.c_void_p), ("losses", C.c_void_p),
+                ("drop_p", C.c_float), ("drop_iteration", C.c_uint32), ("drop_seed", C.c_uint64)]
 
 
 # every symbol include/mdd_hip.h declares: name -> (restype, argtypes)
@@ -50,6 +51,9 @@ SIGNATURES = {
     "mdd_img_tangent_forward": (_I, [_P, _I, _P, _P, _P, _P]),
     "mdd_img_tangent_backward": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _F, _P]),
     "mdd_txt_forward": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
+    "mdd_txt_forward_rng": (_I, [_P, _I, _P, _P, _P, _F, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    "mdd_op_dropout_mask": (_I, [_F, C.c_uint64, C.c_uint32, C.c_uint32, _I, _I, _P, _P, _P]),
+    "mdd_sizeof_iter_args": (C.c_size_t, []),
     "mdd_txt_backward": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _F, _I, _P]),
     "mdd_txt_tangent_forward": (_I, [_P, _I, _P, _P, _P, _P]),
     "mdd_txt_tangent_backward": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _F, _P]),
@@ -148,6 +152,9 @@ def load(variant=None):
     if lib.mdd_version() != ABI_VERSION:      # MddConfig / MddIterArgs layouts below belong to this version
         raise RuntimeError("libmdd_hip.so ABI version %d, this binding expects %d: rebuild (build_ext)"
                            % (lib.mdd_version(), ABI_VERSION))
+    if lib.mdd_sizeof_iter_args() != C.sizeof(MddIterArgs):
+        raise RuntimeError("libmdd_hip.so mdd_iter_args is %d bytes, this binding's MddIterArgs %d: rebuild (build_ext)"
+                           % (lib.mdd_sizeof_iter_args(), C.sizeof(MddIterArgs)))
     _lib = lib
     return lib
 

@@ -71,6 +71,9 @@ def build_parser():
                    help="train on random pairs, this many steps per epoch (no dataset offline)")
     p.add_argument("--compute_dtype", default="bf16", choices=["bf16", "bf16x2", "f32"])
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--dropout_rng", default="torch", choices=["torch", "engine"],
+                   help="who draws the text projection's dropout masks: torch's device RNG or the engine itself "
+                        "(counter-based, from --seed and the global step count alone)")
     p.add_argument("--train_images", type=str, default=None,
                    help="tensor file (.pt/.npy/.npz key 'images') [M,3,S,S]: training images, annotation order")
     p.add_argument("--embed_dir", type=str, default=".",
@@ -122,6 +125,9 @@ def main(args):
             ti, te, i2t, t2i = load_eval_data(args.eval_data, args)
             eval_set = (ti.to(device).contiguous(), te.to(device).contiguous(), i2t, t2i)
         cpu_gen = torch.Generator().manual_seed(args.seed)
+    # --dropout_rng engine: the engine draws the masks from (seed, the global step count)
+    rank = int(os.environ.get("RANK", 0))
+    drop = [0.1, args.seed * 1_000_003 + rank, 0] if args.dropout_rng == "engine" else None
     for it in range(args.num_experts):
         th_i, th_t = synthetic_expert_params(eng, args.seed * 100003 + it, device=device)
         snaps_i, snaps_t = [th_i.cpu()], [th_t.cpu()]          # buffer.py:67-68
@@ -134,7 +140,8 @@ def main(args):
             if real is not None:     # reference buffer.py:73-92: one pass over the training pairs, then metrics
                 train_loss, train_acc, first = ep.train_epoch(
                     eng, th_i, th_t, mom_i, mom_t, real[0], real[1], lr_i, n, first, momentum=args.mom,
-                    weight_decay=args.l2, generator=cpu_gen, lr_txt=lr_t, eng_tail=eng_tail, with_accuracy=True)
+                    weight_decay=args.l2, generator=cpu_gen, lr_txt=lr_t, eng_tail=eng_tail, with_accuracy=True,
+                    dropout=drop)
                 msg = "Itr: {}\tEpoch: {}\tTrain Loss: {:.4f}\tTrain Acc: {:.4f}".format(it, e, train_loss, train_acc)
                 if eval_set is not None:
                     r = ep.epoch_test_metrics(eng, th_i, th_t, *eval_set)
@@ -146,8 +153,12 @@ def main(args):
                 txt = torch.randn(n, d_txt, device=device, generator=g) * 0.5253
                 x = eng.img_forward(0, th_i, img)
                 # the text projection trains with Dropout(0.1) (networks.py:625-646, model.train())
-                mask = (torch.rand(n, eng.feature_dim, device=device, generator=g) >= 0.1).float() / 0.9
-                y = eng.txt_forward(0, th_t, txt, drop_mask=mask)
+                if drop is None:
+                    mask = (torch.rand(n, eng.feature_dim, device=device, generator=g) >= 0.1).float() / 0.9
+                    y = eng.txt_forward(0, th_t, txt, drop_mask=mask)
+                else:
+                    y = eng.txt_forward(0, th_t, txt, dropout=(drop[0], drop[1], 0, drop[2]))
+                    drop[2] += 1
                 _, xb, yb, _ = eng.contrastive(x, y, 1.0 / 0.07)   # networks.py:878
                 gi = eng.img_backward(0, th_i, xb)
                 gt = eng.txt_backward(0, th_t, yb)

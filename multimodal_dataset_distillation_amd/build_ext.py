@@ -18,7 +18,7 @@ SOURCES = ["flat_ops.hip", "ws.hip", "elementwise.hip", "linear.hip", "head.hip"
            "nfres.hip", "nfreg.hip", "conv_g8.hip", "engine.hip"]
 # sources that include another source file: rebuilt when it changes
 INCLUDES = {"conv_gemm_relu.hip": ["conv_gemm.hip"]}
-HEADERS = ["common.h", "kernels.h", "conv_gemm_epilogue.inc", "conv_gemm_epilogue_se.inc", os.path.join("..", "..", "include", "mdd_hip.h")]
+HEADERS = ["common.h", "kernels.h", "philox.h", "conv_gemm_epilogue.inc", "conv_gemm_epilogue_se.inc", os.path.join("..", "..", "include", "mdd_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result",
          "-I", os.path.join(HERE, "..", "include")]
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "philox.h"
 #include "mdd_hip.h"
 
 // ------------------------------------------------------------------------------------------ errors
@@ -188,8 +189,10 @@ struct mdd_engine {
   virtual int img_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar,
                            const float* ybar_t, float* gout, float* dimage, const int64_t* idx,
                            const float* coef, float mul, bool repack, bool stash, hipStream_t st) = 0;
+  // dropout of a primal call: the caller's `mask` tensor, else `drop` (the engine draws the mask itself: philox.h), else
+  // none; the slot remembers which, and the backward / tangent passes of the slot replay it
   virtual int txt_forward(bool T, int slot, const float* th, const float* th_t, const float* text,
-                          const int64_t* idx, const float* mask, float* feat_out,
+                          const int64_t* idx, const float* mask, const DropSpec* drop, float* feat_out,
                           hipStream_t st) = 0;
   virtual int txt_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar,
                            const float* ybar_t, float* gout, float* dtext, const int64_t* idx,
@@ -1740,7 +1743,8 @@ struct Eng : mdd_engine {
 
   // ------------------------------------------------------------------ text projection head
   int txt_forward(bool T, int slot, const float* th, const float* th_t, const float* text,
-                  const int64_t* idx, const float* mask, float* feat_out, hipStream_t st) override {
+                  const int64_t* idx, const float* mask, const DropSpec* drop, float* feat_out,
+                  hipStream_t st) override {
     CHECK_ARG(base, "workspace not bound");
     DevGuard guard(device_id);
     CHECK_ARG(slot >= 0 && slot < nslots, "slot out of range");
@@ -1752,17 +1756,24 @@ struct Eng : mdd_engine {
     launch_gelu(P.tg, T ? Q.tg : nullptr, P.tp, T ? Q.tp : nullptr, (int64_t)N * feat, st);
     launch_linear_fwd(P.tf, T ? Q.tf : nullptr, P.tg, T ? Q.tg : nullptr, th + t_fw, tt(t_fw),
                       th + t_fb, tt(t_fb), N, feat, feat, 0, lin_txt, st);
-    // the dropout mask of this slot is kept for the backward / tangent passes
-    if (!T) slot_mask_[slot] = mask;
+    // the dropout of this slot is kept for the backward / tangent passes: the caller's mask tensor, or what the mask is
+    // drawn from (the row index vector included: those passes are not given it again)
+    if (!T) {
+      SlotDrop& sd = slot_drop_[slot];
+      sd.mask = mask;
+      sd.spec = (drop && !mask) ? *drop : drop_spec_none();
+      sd.spec.idx = idx;
+    }
     launch_ln_fwd(P.ty, T ? feat_out : nullptr, P.tr, T ? Q.tr : nullptr, P.tf, T ? Q.tf : nullptr,
-                  slot_mask_[slot], P.tp, T ? Q.tp : nullptr, th + t_lw, tt(t_lw), th + t_lb,
-                  tt(t_lb), N, feat, 1e-5f, st);
+                  slot_drop_[slot].mask, slot_drop_[slot].spec, P.tp, T ? Q.tp : nullptr, th + t_lw, tt(t_lw),
+                  th + t_lb, tt(t_lb), N, feat, 1e-5f, st);
     if (!T && feat_out && feat_out != P.ty)
       HIP_CHECK_RET(hipMemcpyAsync(feat_out, P.ty, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
     POST_WALK();
     return 0;
   }
-  std::vector<const float*> slot_mask_ = std::vector<const float*>(65, nullptr);
+  struct SlotDrop { const float* mask = nullptr; DropSpec spec = drop_spec_none(); };
+  std::vector<SlotDrop> slot_drop_ = std::vector<SlotDrop>(65);
 
   int txt_backward(bool T, int slot, const float* th, const float* th_t, const float* ybar_in,
                    const float* ybar_t_in, float* gout, float* dtext, const int64_t* idx,
@@ -1777,7 +1788,7 @@ struct Eng : mdd_engine {
       HIP_CHECK_RET(hipMemcpyAsync(O.tyB, ybar_in, (size_t)N * feat * 4, hipMemcpyDeviceToDevice, st));
     launch_ln_bwd(O.trB, T ? Q.trB : nullptr, O.tfB, T ? Q.tfB : nullptr, gout + t_lw, gout + t_lb,
                   ln_stats, O.tyB, T ? ybar_t_in : nullptr, P.tr, T ? Q.tr : nullptr,
-                  slot_mask_[slot], th + t_lw, tt(t_lw), N, feat, 1e-5f, st);
+                  slot_drop_[slot].mask, slot_drop_[slot].spec, th + t_lw, tt(t_lw), N, feat, 1e-5f, st);
     launch_linear_wgrad(gout + t_fw, gout + t_fb, O.tfB, T ? Q.tfB : nullptr, P.tg,
                         T ? Q.tg : nullptr, N, feat, feat, lin_txt, st);
     launch_linear_dgrad(O.tgB, T ? Q.tgB : nullptr, O.tfB, T ? Q.tfB : nullptr, th + t_fw, tt(t_fw),
@@ -1816,6 +1827,8 @@ struct Eng : mdd_engine {
     CHECK_ARG(base, "workspace not bound");
     DevGuard guard(device_id);
     CHECK_ARG(a->syn_steps >= 1 && a->syn_steps <= K, "syn_steps exceeds the engine's slots");
+    CHECK_ARG(drop_p_valid(a->drop_p), "drop_p must lie in [0, 1)");
+    CHECK_ARG(!(a->drop_masks && a->drop_p > 0.f), "drop_masks and drop_p > 0 are both given");
     const int Ks = a->syn_steps;
     const float* scale_dev = a->use_lr_as_scale ? a->lr_img : nullptr;
     const int64_t nfeat = (int64_t)N * feat;
@@ -1830,11 +1843,13 @@ struct Eng : mdd_engine {
     auto primal_step = [&](int k, int slot) -> int {
       const int64_t* idx = a->perms ? a->perms + (int64_t)k * N : nullptr;
       const float* mask = a->drop_masks ? a->drop_masks + (int64_t)k * nfeat : nullptr;
+      // the engine's own mask is drawn for STEP k, whichever slot holds it: the shared slot's recompute draws it again
+      const DropSpec drop = drop_spec(a->drop_p, a->drop_seed, (uint32_t)k, a->drop_iteration, idx);
       ActSet& Pk = sets[slot];
       // the text projection runs on its own stream beside the image encoder; they meet at the
       // contrastive head
       fork_to(ts, st);
-      if ((rc = txt_forward(false, slot, tT[k], nullptr, a->text_syn, idx, mask, nullptr, ts))) return rc;
+      if ((rc = txt_forward(false, slot, tT[k], nullptr, a->text_syn, idx, mask, &drop, nullptr, ts))) return rc;
       if ((rc = img_forward(false, slot, tI[k], nullptr, a->image_syn, idx, nullptr, st))) return rc;
       join_from(ts, st);
       if ((rc = contrastive(false, Pk.y, Pk.ty, nullptr, nullptr, scale_dev,
@@ -1881,7 +1896,7 @@ struct Eng : mdd_engine {
       fork_to(ts, st);
       launch_dot(gT[k], lamT, dsc + 5, -1.0, P_txt, ts);
       launch_scale_out(nuT, lamT, a->lr_txt, 1.f, P_txt, ts);
-      if ((rc = txt_forward(true, slot, tT[k], nuT, nullptr, nullptr, nullptr, fy_t, ts))) return rc;
+      if ((rc = txt_forward(true, slot, tT[k], nuT, nullptr, nullptr, nullptr, nullptr, fy_t, ts))) return rc;
       launch_dot(gI[k], lamI, dsc + 4, -1.0, P_img, st);   // d/d lr_img  -= <g_k, lambda>
       launch_scale_out(nuI, lamI, a->lr_img, 1.f, P_img, st);  // direction v = lr * lambda
       if ((rc = img_forward(true, slot, tI[k], nuI, nullptr, nullptr, fx_t, st))) return rc;
@@ -1911,6 +1926,7 @@ extern "C" {
 
 const char* mdd_last_error(void) { return g_err.c_str(); }
 int mdd_version(void) { return MDD_ABI_VERSION; }
+size_t mdd_sizeof_iter_args(void) { return sizeof(mdd_iter_args); }
 int mdd_set_pipe_kernels(int enable) {
   const int prev = pipe_kernels_enabled() ? 1 : 0;
   set_pipe_kernels(enable != 0);
@@ -2014,7 +2030,22 @@ int mdd_img_tangent_backward(mdd_engine* e, int slot, const float* th, const flo
 int mdd_txt_forward(mdd_engine* e, int slot, const float* th, const float* text,
                     const int64_t* idx, const float* mask, float* feat_out, void* stream) {
   CHECK_ARG(e && th && text, "null pointer");
-  return e->txt_forward(false, slot, th, nullptr, text, idx, mask, feat_out, (hipStream_t)stream);
+  return e->txt_forward(false, slot, th, nullptr, text, idx, mask, nullptr, feat_out, (hipStream_t)stream);
+}
+int mdd_txt_forward_rng(mdd_engine* e, int slot, const float* th, const float* text, const int64_t* idx, float p,
+                        uint64_t seed, uint32_t step, uint32_t iteration, float* feat_out, void* stream) {
+  CHECK_ARG(e && th && text, "null pointer");
+  CHECK_ARG(drop_p_valid(p), "p must lie in [0, 1)");
+  const DropSpec drop = drop_spec(p, seed, step, iteration, idx);
+  return e->txt_forward(false, slot, th, nullptr, text, idx, nullptr, &drop, feat_out, (hipStream_t)stream);
+}
+int mdd_op_dropout_mask(float p, uint64_t seed, uint32_t step, uint32_t iteration, int n, int d, const int64_t* idx,
+                        float* out, void* stream) {
+  CHECK_ARG(out && n >= 1 && d >= 1, "null pointer or empty shape");
+  CHECK_ARG(drop_p_valid(p), "p must lie in [0, 1)");
+  launch_dropout_mask(out, drop_spec(p, seed, step, iteration, idx), n, d, (hipStream_t)stream);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
 }
 int mdd_txt_backward(mdd_engine* e, int slot, const float* th, const float* fb, float* gout,
                      float* dtext, const int64_t* idx, const float* coef, float mul, int stash,
@@ -2026,7 +2057,7 @@ int mdd_txt_backward(mdd_engine* e, int slot, const float* th, const float* fb, 
 int mdd_txt_tangent_forward(mdd_engine* e, int slot, const float* th, const float* thd,
                             float* fdot, void* stream) {
   CHECK_ARG(e && th && thd && fdot, "null pointer");
-  return e->txt_forward(true, slot, th, thd, nullptr, nullptr, nullptr, fdot, (hipStream_t)stream);
+  return e->txt_forward(true, slot, th, thd, nullptr, nullptr, nullptr, nullptr, fdot, (hipStream_t)stream);
 }
 int mdd_txt_tangent_backward(mdd_engine* e, int slot, const float* th, const float* thd,
                              const float* fbd, float* hout, float* dtext, const int64_t* idx,
@@ -2395,13 +2426,13 @@ int mdd_op_text_head(int op, int n, int d, float eps, float mul, const float* a,
       CHECK_ARG(b && gamma && beta && out2 && !c && !c_t, "ln_fwd: f, p, gamma, beta, y, r");
       CHECK_ARG(T == (b_t != nullptr) && T == (out2_t != nullptr), "ln_fwd tangent: f_t, p_t, y_t, r_t");
       CHECK_ARG(!dgamma && !dbeta && !stats, "ln_fwd has no parameter gradients");
-      launch_ln_fwd(out, out_t, out2, out2_t, a, a_t, mask, b, b_t, gamma, gamma_t, beta, beta_t, n, d, eps, st);
+      launch_ln_fwd(out, out_t, out2, out2_t, a, a_t, mask, drop_spec_none(), b, b_t, gamma, gamma_t, beta, beta_t, n, d, eps, st);
       break;
     case 3:   // a = ybar, b = r -> out = rbar, out2 = fbar = rbar * mask, dgamma, dbeta (tangent: their tangents)
       CHECK_ARG(b && gamma && out2 && dgamma && dbeta && stats && !c && !c_t && !beta && !beta_t,
                 "ln_bwd: ybar, r, gamma, rbar, fbar, dgamma, dbeta, stats [4 n]");
       CHECK_ARG(T == (b_t != nullptr) && T == (out2_t != nullptr), "ln_bwd tangent: ybar_t, r_t, rbar_t, fbar_t");
-      launch_ln_bwd(out, out_t, out2, out2_t, dgamma, dbeta, stats, a, a_t, b, b_t, mask, gamma, gamma_t, n, d, eps, st);
+      launch_ln_bwd(out, out_t, out2, out2_t, dgamma, dbeta, stats, a, a_t, b, b_t, mask, drop_spec_none(), gamma, gamma_t, n, d, eps, st);
       break;
     case 4:   // out [n, d] = a[idx]
       CHECK_ARG(!T && !b && !c && !coef, "gather_rows: in, idx");

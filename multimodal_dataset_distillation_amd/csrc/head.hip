@@ -4,6 +4,7 @@
 // and -- via S = Dual -- the tangent of forward and backward.  fp32 throughout (the reference
 // calls .float() here); wavefront/LDS reductions for LayerNorm and softmax.
 #include "kernels.h"
+#include "philox.h"
 
 namespace {
 
@@ -36,6 +37,12 @@ __global__ void k_gelu_bwd(float* __restrict__ pbar, float* __restrict__ pbar_t,
   }
 }
 
+// dropout mask of (row, column i): the caller's tensor wins, else the engine's own draw (drop.p > 0), else 1
+DEVI float mask_at(const float* mask, const DropSpec& drop, int row, int i, size_t gi) {
+  if (mask) return mask[gi];
+  return drop.p > 0.f ? drop_mask_value(drop, row, i) : 1.f;
+}
+
 template <class S> struct LnStats { S mu, rstd; };
 template <class S>
 DEVI LnStats<S> ln_stats(const float* r, const float* r_t, int d, float eps, float* scratch) {
@@ -60,14 +67,14 @@ template <class S>
 __global__ void k_ln_fwd(float* __restrict__ y, float* __restrict__ y_t, float* __restrict__ r,
                          float* __restrict__ r_t, const float* __restrict__ f,
                          const float* __restrict__ f_t, const float* __restrict__ mask,
-                         const float* __restrict__ p, const float* __restrict__ p_t,
+                         DropSpec drop, const float* __restrict__ p, const float* __restrict__ p_t,
                          const float* __restrict__ gamma, const float* __restrict__ gamma_t,
                          const float* __restrict__ beta, const float* __restrict__ beta_t, int d,
                          float eps) {
   __shared__ float scratch[16];
   size_t base = (size_t)blockIdx.x * d;
   for (int i = threadIdx.x; i < d; i += blockDim.x) {
-    S v = ldS<S>(f, f_t, base + i) * (mask ? mask[base + i] : 1.f) + ldS<S>(p, p_t, base + i);
+    S v = ldS<S>(f, f_t, base + i) * mask_at(mask, drop, blockIdx.x, i, base + i) + ldS<S>(p, p_t, base + i);
     stS<S>(r, r_t, base + i, v);
   }
   __syncthreads();
@@ -87,8 +94,8 @@ __global__ void k_ln_bwd_rows(float* __restrict__ rbar, float* __restrict__ rbar
                               float* __restrict__ stats, const float* __restrict__ ybar,
                               const float* __restrict__ ybar_t, const float* __restrict__ r,
                               const float* __restrict__ r_t, const float* __restrict__ mask,
-                              const float* __restrict__ gamma, const float* __restrict__ gamma_t,
-                              int d, float eps) {
+                              DropSpec drop, const float* __restrict__ gamma,
+                              const float* __restrict__ gamma_t, int d, float eps) {
   __shared__ float scratch[16];
   size_t base = (size_t)blockIdx.x * d;
   LnStats<S> st = ln_stats<S>(r + base, IsDual<S>::v ? r_t + base : nullptr, d, eps, scratch);
@@ -107,7 +114,7 @@ __global__ void k_ln_bwd_rows(float* __restrict__ rbar, float* __restrict__ rbar
     S rh = (ldS<S>(r, r_t, base + i) - st.mu) * st.rstd;
     S rb = st.rstd * (gy - m1 - rh * m2);
     stS<S>(rbar, rbar_t, base + i, rb);
-    stS<S>(fbar, fbar_t, base + i, rb * (mask ? mask[base + i] : 1.f));
+    stS<S>(fbar, fbar_t, base + i, rb * mask_at(mask, drop, blockIdx.x, i, base + i));
   }
   if (threadIdx.x == 0) {
     stats[blockIdx.x * 4 + 0] = val(st.mu);
@@ -308,6 +315,22 @@ __global__ void k_scatter_rows_axpy(float* __restrict__ out, const float* __rest
   }
 }
 
+// out[row, 4q .. 4q + 3] = the engine's dropout mask (philox.h); a thread per quad of columns, the last quad of a row cut at d
+__global__ void k_dropout_mask(float* __restrict__ out, DropSpec drop, int n, int d) {
+  const int qpr = (d + 3) >> 2;
+  const int64_t total = (int64_t)n * qpr;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int row = (int)(t / qpr), q = (int)(t - (int64_t)row * qpr);
+    const Philox4 w = drop_quad(drop, row, (uint32_t)q);
+    float* o = out + (int64_t)row * d;
+    const int c = q << 2;
+    o[c] = drop_word_value(drop, w.w0);
+    if (c + 1 < d) o[c + 1] = drop_word_value(drop, w.w1);
+    if (c + 2 < d) o[c + 2] = drop_word_value(drop, w.w2);
+    if (c + 3 < d) o[c + 3] = drop_word_value(drop, w.w3);
+  }
+}
+
 inline int pgrid(int64_t n) {
   int64_t g = (n + 255) / 256;
   return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
@@ -323,6 +346,9 @@ void launch_scatter_rows_axpy(float* out, const float* in, const int64_t* idx, c
                               float mul, int n, int d, hipStream_t st) {
   k_scatter_rows_axpy<<<pgrid((int64_t)n * d), 256, 0, st>>>(out, in, idx, coef, mul, n, d);
 }
+void launch_dropout_mask(float* out, const DropSpec& drop, int n, int d, hipStream_t st) {
+  k_dropout_mask<<<pgrid((int64_t)n * ((d + 3) / 4)), 256, 0, st>>>(out, drop, n, d);
+}
 void launch_gelu(float* g, float* g_t, const float* p, const float* p_t, int64_t n, hipStream_t st) {
   if (g_t) k_gelu<Dual><<<pgrid(n), 256, 0, st>>>(g, g_t, p, p_t, n);
   else k_gelu<float><<<pgrid(n), 256, 0, st>>>(g, nullptr, p, nullptr, n);
@@ -334,21 +360,21 @@ void launch_gelu_bwd(float* pbar, float* pbar_t, const float* rbar, const float*
   else k_gelu_bwd<float><<<pgrid(n), 256, 0, st>>>(pbar, nullptr, rbar, nullptr, gbar, nullptr, p, nullptr, n);
 }
 void launch_ln_fwd(float* y, float* y_t, float* r, float* r_t, const float* f, const float* f_t,
-                   const float* mask, const float* p, const float* p_t, const float* gamma,
-                   const float* gamma_t, const float* beta, const float* beta_t, int n, int d,
-                   float eps, hipStream_t st) {
-  if (y_t) k_ln_fwd<Dual><<<n, 256, 0, st>>>(y, y_t, r, r_t, f, f_t, mask, p, p_t, gamma, gamma_t, beta, beta_t, d, eps);
-  else k_ln_fwd<float><<<n, 256, 0, st>>>(y, nullptr, r, nullptr, f, nullptr, mask, p, nullptr, gamma, nullptr, beta, nullptr, d, eps);
+                   const float* mask, const DropSpec& drop, const float* p, const float* p_t,
+                   const float* gamma, const float* gamma_t, const float* beta, const float* beta_t, int n,
+                   int d, float eps, hipStream_t st) {
+  if (y_t) k_ln_fwd<Dual><<<n, 256, 0, st>>>(y, y_t, r, r_t, f, f_t, mask, drop, p, p_t, gamma, gamma_t, beta, beta_t, d, eps);
+  else k_ln_fwd<float><<<n, 256, 0, st>>>(y, nullptr, r, nullptr, f, nullptr, mask, drop, p, nullptr, gamma, nullptr, beta, nullptr, d, eps);
 }
 void launch_ln_bwd(float* rbar, float* rbar_t, float* fbar, float* fbar_t, float* dgamma,
                    float* dbeta, float* stats, const float* ybar, const float* ybar_t,
-                   const float* r, const float* r_t, const float* mask, const float* gamma,
-                   const float* gamma_t, int n, int d, float eps, hipStream_t st) {
+                   const float* r, const float* r_t, const float* mask, const DropSpec& drop,
+                   const float* gamma, const float* gamma_t, int n, int d, float eps, hipStream_t st) {
   if (rbar_t) {
-    k_ln_bwd_rows<Dual><<<n, 256, 0, st>>>(rbar, rbar_t, fbar, fbar_t, stats, ybar, ybar_t, r, r_t, mask, gamma, gamma_t, d, eps);
+    k_ln_bwd_rows<Dual><<<n, 256, 0, st>>>(rbar, rbar_t, fbar, fbar_t, stats, ybar, ybar_t, r, r_t, mask, drop, gamma, gamma_t, d, eps);
     k_ln_bwd_cols<Dual><<<(d + 255) / 256, 256, 0, st>>>(dgamma, dbeta, stats, ybar, ybar_t, r, r_t, n, d);
   } else {
-    k_ln_bwd_rows<float><<<n, 256, 0, st>>>(rbar, nullptr, fbar, nullptr, stats, ybar, nullptr, r, nullptr, mask, gamma, nullptr, d, eps);
+    k_ln_bwd_rows<float><<<n, 256, 0, st>>>(rbar, nullptr, fbar, nullptr, stats, ybar, nullptr, r, nullptr, mask, drop, gamma, nullptr, d, eps);
     k_ln_bwd_cols<float><<<(d + 255) / 256, 256, 0, st>>>(dgamma, dbeta, stats, ybar, nullptr, r, nullptr, n, d);
   }
 }

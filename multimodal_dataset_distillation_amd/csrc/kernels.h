@@ -287,16 +287,21 @@ void launch_gather_rows(float* out, const float* in, const int64_t* idx, int n, 
 void launch_scatter_rows_axpy(float* out, const float* in, const int64_t* idx, const float* coef,
                               float mul, int n, int d, hipStream_t st);
 void launch_gelu(float* g, float* g_t, const float* p, const float* p_t, int64_t n, hipStream_t st);
+// The dropout mask of the two kernels below: the caller's tensor `mask` when given, else the engine's own draw when
+// drop.p > 0 (philox.h: regenerated in every pass, nothing stored), else 1.
+struct DropSpec;
 // r = f*mask + p ; y = LN(r)*gamma + beta
 void launch_ln_fwd(float* y, float* y_t, float* r, float* r_t, const float* f, const float* f_t,
-                   const float* mask, const float* p, const float* p_t, const float* gamma,
-                   const float* gamma_t, const float* beta, const float* beta_t, int n, int d,
-                   float eps, hipStream_t st);
+                   const float* mask, const DropSpec& drop, const float* p, const float* p_t,
+                   const float* gamma, const float* gamma_t, const float* beta, const float* beta_t, int n,
+                   int d, float eps, hipStream_t st);
 // rbar (LN backward wrt r), fbar = rbar*mask; dgamma/dbeta
 void launch_ln_bwd(float* rbar, float* rbar_t, float* fbar, float* fbar_t, float* dgamma,
                    float* dbeta, float* stats /*[n*4] scratch*/, const float* ybar, const float* ybar_t, const float* r,
-                   const float* r_t, const float* mask, const float* gamma, const float* gamma_t,
-                   int n, int d, float eps, hipStream_t st);
+                   const float* r_t, const float* mask, const DropSpec& drop, const float* gamma,
+                   const float* gamma_t, int n, int d, float eps, hipStream_t st);
+// out [n, d] = the mask itself
+void launch_dropout_mask(float* out, const DropSpec& drop, int n, int d, hipStream_t st);
 // pbar = rbar + gbar*dgelu(p)
 void launch_gelu_bwd(float* pbar, float* pbar_t, const float* rbar, const float* rbar_t,
                      const float* gbar, const float* gbar_t, const float* p, const float* p_t,

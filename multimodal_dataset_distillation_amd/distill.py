@@ -113,6 +113,10 @@ def build_parser():
                         "--buffer_path (no dataset/pretrained weights exist offline)")
     p.add_argument("--save_dir", type=str, default=None)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--dropout_rng", default="torch", choices=["torch", "engine"],
+                   help="who draws the student text projection's dropout masks: torch's device RNG (a mask tensor per "
+                        "iteration) or the engine itself (counter-based, from --seed and the iteration number alone; "
+                        "nothing is stored)")
     p.add_argument("--keep_steps", type=int, default=None,
                    help="activation stash policy: keep the activations of the first KEEP inner steps in "
                         "HBM, recompute the others during the outer backward (default: keep all)")
@@ -219,7 +223,8 @@ def run_evaluation(args, it, image_syn, text_syn, syn_lr_img, eval_set, eval_eng
         lr_net = float(syn_lr_img)                      # args.lr_net = syn_lr_img.item()  (distill.py:312)
         _, _, res = evaluate_synset(eng_e, image_syn.detach().clone(), text_syn.detach().clone(), test_images,
                                     test_embed, img2txt, txt2img, lr_net=lr_net,
-                                    epoch_eval_train=args.epoch_eval_train, seed=args.seed * 1009 + it * 31 + it_eval)
+                                    epoch_eval_train=args.epoch_eval_train, seed=args.seed * 1009 + it * 31 + it_eval,
+                                    dropout_rng=args.dropout_rng)
         print("Evaluate_%02d: Img R@1 = %.4f, Img R@5 = %.4f, Img R@10 = %.4f, Img R@Mean = %.4f, "
               "Txt R@1 = %.4f, Txt R@5 = %.4f, Txt R@10 = %.4f, Txt R@Mean = %.4f, R@Mean = %.4f"
               % ((it_eval,) + tuple(res[k] for k in keys)))
@@ -309,6 +314,11 @@ def main(args):
                        d_txt=d_txt, syn_steps=args.syn_steps, dtype=args.compute_dtype, device=device,
                        keep_steps=args.keep_steps)
     lib = _lib.load()
+    # --dropout_rng engine: mode B draws ONE mask per minibatch, so every rank uses the same seed; otherwise every
+    # rank trains its own student
+    engine_drop = args.dropout_rng == "engine"
+    drop_seed = args.seed if mode_b else args.seed * 1_000_003 + rank
+    args.dropout_seed = drop_seed
     from .embed_cache import load_embed_cache, load_eval_data
     # ---- on-disk inputs around the loop (distill.py:221-229): caption-embedding caches
     train_caption_embed = train_sentences = None
@@ -398,19 +408,22 @@ def main(args):
 
         if mode_b:
             from . import parallel as par
-            gm = torch.Generator(device=device).manual_seed(args.seed * 1_000_003 + it)   # same masks on every rank
-            masks = (torch.rand(args.syn_steps, batch, eng.feature_dim, device=device, generator=gm) >= 0.1).float() / 0.9
+            masks = None
+            if not engine_drop:
+                gm = torch.Generator(device=device).manual_seed(args.seed * 1_000_003 + it)   # same masks on every rank
+                masks = (torch.rand(args.syn_steps, batch, eng.feature_dim, device=device, generator=gm) >= 0.1).float() / 0.9
             ob = par.run_collectives(par.sharded_unrolled_match(
                 eng, rank, world, image_syn, text_syn, lr, th0i, th0t, tgi, tgt, perms, drop_masks=masks,
-                logit_scale=args.logit_scale))
+                logit_scale=args.logit_scale, dropout=(0.1, drop_seed, it) if engine_drop else None))
             out["image_syn"].copy_(ob["image_syn"]), out["text_syn"].copy_(ob["text_syn"]), out["lr"].copy_(ob["lr"])
             losses = torch.cat([torch.stack([ob["grand_loss"], ob["img_loss"], ob["txt_loss"]]), ob["contrastive"]])
         elif args.engine == "fused":
             masks = None
-            if True:  # the student text projection is in train mode (distill.py:446-447): Dropout(0.1)
+            if not engine_drop:  # the student text projection is in train mode (distill.py:446-447): Dropout(0.1)
                 masks = (torch.rand(args.syn_steps, batch, eng.feature_dim, device=device) >= 0.1).float() / 0.9
             eng.unrolled_match(image_syn, text_syn, lr[0:1], lr[1:2], th0i, th0t, tgi, tgt, perms=perms,
-                               drop_masks=masks, logit_scale=args.logit_scale, out=out)
+                               drop_masks=masks, logit_scale=args.logit_scale, out=out,
+                               dropout=(0.1, drop_seed, it) if engine_drop else None)
             losses = out["losses"]
         else:
             img_r = image_syn.detach().requires_grad_(True)

@@ -36,6 +36,21 @@ def _f32(t):
     return t
 
 
+def dropout_mask(p, seed, step, iteration, n, d, idx=None, device="cuda", out=None):
+    """The [n, d] mask the engine draws for (p, seed, step, iteration) (include/mdd_hip.h mdd_txt_forward_rng): row r is
+    the mask of sample idx[r] (int64 device tensor), or of sample r.  Values 0 or 1 / (1 - p)."""
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(int(n), int(d), dtype=torch.float32, device=device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == int(n) * int(d)
+    if idx is not None:
+        assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == int(n)
+    with torch.cuda.device(out.device):
+        check(lib.mdd_op_dropout_mask(float(p), int(seed) & (2**64 - 1), int(step), int(iteration), int(n), int(d),
+                                      _ptr(idx), _ptr(out), _stream()))
+    return out
+
+
 class UnrollEngine:
     def __init__(self, variant="nfnet_l0", batch=100, num_queries=None, image_size=224, d_txt=768,
                  syn_steps=8, dtype="bf16", device="cuda", bind=True, keep_steps=None):
@@ -148,12 +163,23 @@ class UnrollEngine:
                                                 _ptr(idx), _ptr(coef), float(mul), _stream()))
         return h
 
-    def txt_forward(self, slot, theta, text_syn, idx=None, drop_mask=None):
+    def txt_forward(self, slot, theta, text_syn, idx=None, drop_mask=None, dropout=None):
+        """drop_mask: a pre-scaled [batch, feat] mask tensor; dropout = (p, seed, step, iteration): the engine draws the
+        mask itself and the backward / tangent passes of the slot draw it again (nothing is stored)."""
         out = self._new(self.batch, self.feature_dim)
         self._keep = getattr(self, "_keep", {})
         self._keep[("mask", slot)] = drop_mask  # the engine reads it again in backward/tangent
-        check(self.lib.mdd_txt_forward(self.h, slot, _ptr(_f32(theta)), _ptr(_f32(text_syn)),
-                                       _ptr(idx), _ptr(drop_mask), _ptr(out), _stream()))
+        if dropout is None:
+            check(self.lib.mdd_txt_forward(self.h, slot, _ptr(_f32(theta)), _ptr(_f32(text_syn)),
+                                           _ptr(idx), _ptr(drop_mask), _ptr(out), _stream()))
+            return out
+        if drop_mask is not None:
+            raise ValueError("txt_forward: give drop_mask or dropout, not both")
+        p, seed, step, iteration = dropout
+        self._keep[("idx", slot)] = idx         # the row ids are part of what the later passes draw the mask from
+        check(self.lib.mdd_txt_forward_rng(self.h, slot, _ptr(_f32(theta)), _ptr(_f32(text_syn)), _ptr(idx),
+                                           float(p), int(seed) & (2**64 - 1), int(step), int(iteration), _ptr(out),
+                                           _stream()))
         return out
 
     def txt_backward(self, slot, theta, feat_bar, dtext=None, idx=None, coef=None, mul=1.0,
@@ -204,10 +230,12 @@ class UnrollEngine:
     # ------------------------------------------------------------------ whole iteration
     def unrolled_match(self, image_syn, text_syn, lr_img, lr_txt, theta0_img, theta0_txt,
                        target_img, target_txt, perms=None, drop_masks=None, syn_steps=None,
-                       logit_scale=None, out=None):
+                       logit_scale=None, out=None, dropout=None):
         """One outer iteration (reference distill.py:509-606).  Returns dict with `grand_loss`,
         `img_loss`, `txt_loss`, `contrastive` [K] and grads `image_syn`, `text_syn`, `lr` [2]
-        (all device tensors; nothing is synchronised)."""
+        (all device tensors; nothing is synchronised).
+        Text dropout: drop_masks [K, batch, feat] (pre-scaled tensors), or dropout = (p, seed, iteration): the engine
+        draws step k's mask itself in every pass that needs it."""
         K = self.syn_steps if syn_steps is None else int(syn_steps)
         if out is None:
             out = dict(image_syn=torch.empty_like(image_syn), text_syn=torch.empty_like(text_syn),
@@ -224,6 +252,8 @@ class UnrollEngine:
         a.logit_scale_const = 0.0 if logit_scale is None else float(logit_scale)
         a.grad_image_syn, a.grad_text_syn = out["image_syn"].data_ptr(), out["text_syn"].data_ptr()
         a.grad_lr, a.losses = out["lr"].data_ptr(), out["losses"].data_ptr()
+        if dropout is not None:
+            a.drop_p, a.drop_seed, a.drop_iteration = float(dropout[0]), int(dropout[1]) & (2**64 - 1), int(dropout[2])
         for t in (image_syn, text_syn, lr_img, lr_txt, theta0_img, theta0_txt, target_img, target_txt):
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
         if perms is not None:

@@ -110,13 +110,16 @@ def _train_accuracy(x, y):
 
 def train_epoch(eng, theta_img, theta_txt, mom_img, mom_txt, images, texts, lr, batch, first,
                 momentum=0.9, weight_decay=5e-4, generator=None, lr_txt=None, eng_tail=None,
-                with_accuracy=False):
+                with_accuracy=False, dropout=None):
     """One epoch of reference `epoch` (epoch.py:59-98): shuffled mini-batches of (image, caption embedding)
     pairs, forward + fixed-scale (1/0.07) contrastive loss + backward + one SGD step per network
     (`optim.sgd_step` = torch.optim.SGD(lr, momentum, weight_decay)); in place on theta_*/mom_*.
     Defaults are evaluate_synset's optimisers (epoch.py:361-362); buffer.py passes --mom/--l2 and the two
     teacher learning rates.  The engine's batch is fixed: a ragged last batch runs on `eng_tail` (an
     engine of that batch size) when one is given and is dropped otherwise.  One host sync per epoch.
+    dropout: None = the text projection's Dropout(0.1) masks come from torch's device RNG; a list [p, seed, count] =
+    the engine draws them itself with iteration = count, which this function advances by one per step (the caller's
+    global step count).
     Returns (mean loss, first-step flag) or (mean loss, mean accuracy, first-step flag)."""
     from .optim import sgd_step
     n = images.shape[0]
@@ -134,8 +137,12 @@ def train_epoch(eng, theta_img, theta_txt, mom_img, mom_txt, images, texts, lr, 
             e = eng_tail
         b = idx.numel()
         x = e.img_forward(0, theta_img, images, idx=idx)
-        mask = (torch.rand(b, e.feature_dim, device=images.device) >= 0.1).float() / 0.9
-        y = e.txt_forward(0, theta_txt, texts, idx=idx, drop_mask=mask)
+        if dropout is None:
+            mask = (torch.rand(b, e.feature_dim, device=images.device) >= 0.1).float() / 0.9
+            y = e.txt_forward(0, theta_txt, texts, idx=idx, drop_mask=mask)
+        else:
+            y = e.txt_forward(0, theta_txt, texts, idx=idx, dropout=(dropout[0], dropout[1], 0, dropout[2]))
+            dropout[2] += 1
         loss, xb, yb, _ = e.contrastive(x, y, LOGIT_SCALE)
         gi = e.img_backward(0, theta_img, xb)
         gt = e.txt_backward(0, theta_txt, yb)
@@ -153,18 +160,20 @@ def train_epoch(eng, theta_img, theta_txt, mom_img, mom_txt, images, texts, lr, 
 
 
 def evaluate_synset(eng, image_syn, text_syn, test_images, text_embeds, img2txt, txt2img, lr_net=0.1,
-                    epoch_eval_train=1, seed=0):
+                    epoch_eval_train=1, seed=0, dropout_rng="torch"):
     """reference evaluate_synset (epoch.py:348-397): a FRESH student trained on the synthetic pairs for
-    epoch_eval_train+1 epochs, then retrieval metrics.  eng.batch must divide into the synthetic set."""
+    epoch_eval_train+1 epochs, then retrieval metrics.  eng.batch must divide into the synthetic set.
+    dropout_rng="engine": the student's dropout masks are drawn by the engine from (seed, the step count)."""
     from .networks import synthetic_expert_params
     dev = image_syn.device
     theta_img, theta_txt = synthetic_expert_params(eng, seed, device=dev)
     mom_img, mom_txt = torch.zeros_like(theta_img), torch.zeros_like(theta_txt)
     g = torch.Generator().manual_seed(seed)
     first, losses = True, []
+    drop = [0.1, seed, 0] if dropout_rng == "engine" else None
     for ep in range(int(epoch_eval_train) + 1):
         l, first = train_epoch(eng, theta_img, theta_txt, mom_img, mom_txt, image_syn, text_syn, lr_net,
-                               eng.batch, first, generator=g)
+                               eng.batch, first, generator=g, dropout=drop)
         if math.isnan(l):
             break
         losses.append(l)

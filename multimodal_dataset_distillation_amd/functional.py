@@ -73,8 +73,8 @@ class _ImgB(torch.autograd.Function):
 
 class _TxtF(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, theta, x, eng, slot, mask):
-        y = eng.txt_forward(slot, _chk(theta.detach()), _chk(x.detach()), None, mask)
+    def forward(ctx, theta, x, eng, slot, mask, dropout=None):
+        y = eng.txt_forward(slot, _chk(theta.detach()), _chk(x.detach()), None, mask, dropout=dropout)
         ctx.eng, ctx.slot = eng, slot
         ctx.save_for_backward(theta, x)
         ctx.first = True
@@ -86,7 +86,7 @@ class _TxtF(torch.autograd.Function):
         stash = ctx.first
         ctx.first = False
         gtheta, gx = _TxtB.apply(theta, x, ybar, ctx.eng, ctx.slot, stash)
-        return gtheta, gx, None, None, None
+        return gtheta, gx, None, None, None, None
 
 
 class _TxtB(torch.autograd.Function):
@@ -120,9 +120,10 @@ def image_encoder(eng, slot, theta, x):
     return _ImgF.apply(theta, x, eng, slot)
 
 
-def text_projection(eng, slot, theta, x, drop_mask=None):
-    """y = ProjectionHead(x; theta) with an optional pre-scaled dropout mask."""
-    return _TxtF.apply(theta, x, eng, slot, drop_mask)
+def text_projection(eng, slot, theta, x, drop_mask=None, dropout=None):
+    """y = ProjectionHead(x; theta) with an optional pre-scaled dropout mask, or with dropout = (p, seed, step,
+    iteration): the engine draws the mask; the slot remembers it for the backward and double-backward."""
+    return _TxtF.apply(theta, x, eng, slot, drop_mask, dropout)
 
 
 class _Contrastive(torch.autograd.Function):

@@ -152,11 +152,13 @@ class ImageEncoder(nn.Module):
 
 
 class ProjectionHead(nn.Module):
-    """reference networks.py:625-646.  Dropout is active in train mode (distill.py:446-447): the mask
-    is drawn with torch's device RNG and replayed by the engine in backward / double-backward."""
+    """reference networks.py:625-646.  Dropout is active in train mode (distill.py:446-447).  rng="torch": the mask
+    is drawn with torch's device RNG and replayed by the engine in backward / double-backward; rng="engine": the
+    engine draws it from (seed, iteration = the number of forwards this module has run, step = the slot) in every pass
+    and no mask tensor exists."""
 
     def __init__(self, embedding_dim, projection_dim=768, dropout=0.1, image_size=224,
-                 variant="nfnet_l0", syn_steps=8, dtype="bf16"):
+                 variant="nfnet_l0", syn_steps=8, dtype="bf16", rng="torch", seed=0):
         super().__init__()
         self.projection = nn.Linear(embedding_dim, projection_dim)
         self.gelu = nn.GELU()
@@ -166,6 +168,9 @@ class ProjectionHead(nn.Module):
         self.embedding_dim, self.projection_dim, self.p = embedding_dim, projection_dim, dropout
         self.image_size, self.variant, self.syn_steps, self.compute_dtype = image_size, variant, syn_steps, dtype
         self._slot = 0
+        if rng not in ("torch", "engine"):
+            raise ValueError("ProjectionHead rng: 'torch' or 'engine', got %r" % (rng,))
+        self.rng, self.seed = rng, int(seed)
 
     def forward_flat(self, flat_param, x):
         eng = get_engine(self.variant, x.shape[0], self.image_size, self.embedding_dim,
@@ -174,8 +179,11 @@ class ProjectionHead(nn.Module):
             raise RuntimeError("projection_dim %d does not match the %s feature dim %d"
                                % (self.projection_dim, self.variant, eng.feature_dim))
         slot = self._slot % eng.syn_steps
+        count = self._slot
         self._slot += 1
         mask = None
+        if self.training and self.p > 0 and self.rng == "engine":
+            return Fn.text_projection(eng, slot, flat_param, x, dropout=(self.p, self.seed, slot, count))
         if self.training and self.p > 0:
             mask = (torch.rand(x.shape[0], self.projection_dim, device=x.device) >= self.p).float()
             mask = mask / (1.0 - self.p)
@@ -206,7 +214,8 @@ class CLIPModel_full(nn.Module):
         self.text_projection = ProjectionHead(
             embedding_dim=self.text_embedding, projection_dim=self.image_embedding,
             image_size=getattr(args, "image_size", 224), variant=self.image_encoder.variant,
-            syn_steps=self.image_encoder.syn_steps, dtype=self.image_encoder.compute_dtype)
+            syn_steps=self.image_encoder.syn_steps, dtype=self.image_encoder.compute_dtype,
+            rng=getattr(args, "dropout_rng", "torch"), seed=getattr(args, "dropout_seed", getattr(args, "seed", 0)))
         self.temperature = temperature
         self.args = args
         self.distill = getattr(args, "distill", False)

@@ -180,11 +180,13 @@ def _op_contrastive(lib, x, y, scale, xd=None, yd=None):
 
 
 def sharded_unrolled_match(eng, rank, world, image_syn, text_syn, lr, theta0_img, theta0_txt, target_img,
-                           target_txt, perms, drop_masks=None, logit_scale=None):
+                           target_txt, perms, drop_masks=None, logit_scale=None, dropout=None):
     """One outer iteration (reference distill.py:509-606) on shard `rank` of `world`.
     eng: UnrollEngine(batch = minibatch/world, num_queries = len(image_syn)); image_syn/text_syn/theta/lr
     replicated; perms [K, minibatch] and drop_masks [K, minibatch, D] are the FULL minibatch's, identical
-    on every rank.  Returns dict(grand_loss, img_loss, txt_loss, contrastive [K], image_syn, text_syn, lr)
+    on every rank.  dropout = (p, seed, iteration), the same on every rank, instead of drop_masks: the engine draws
+    the masks itself, keyed by sample id, so this shard's rows of perms[k] get exactly the rows of the full
+    minibatch's mask and nothing is sliced.  Returns dict(grand_loss, img_loss, txt_loss, contrastive [K], image_syn, text_syn, lr)
     with the synthetic-set gradients already summed over ranks."""
     from . import _lib
     lib = _lib.load()
@@ -200,7 +202,8 @@ def sharded_unrolled_match(eng, rank, world, image_syn, text_syn, lr, theta0_img
         idx = perms[k, lo:hi].contiguous()
         mask = None if drop_masks is None else drop_masks[k, lo:hi].contiguous()
         x = eng.img_forward(k, thI[k], image_syn, idx=idx)
-        y = eng.txt_forward(k, thT[k], text_syn, idx=idx, drop_mask=mask)
+        drop = None if dropout is None else (dropout[0], dropout[1], k, dropout[2])
+        y = eng.txt_forward(k, thT[k], text_syn, idx=idx, drop_mask=mask, dropout=drop)
         X = yield ("all_gather", x)
         Y = yield ("all_gather", y)
         loss, xb, yb, _ = _op_contrastive(lib, X, Y, scale)
