@@ -49,7 +49,8 @@ typedef struct mdd_engine mdd_engine;
 
 typedef struct mdd_config {
   const char* variant; /* "nfnet_l0" | "nfnet_l1" | "nfnet_tiny" | "nf_resnet50" | "nf_resnet_tiny" | "nf_regnet_b1" |
-                          "nf_regnet_tiny" | "vit_b16" | "vit_tiny16" | "vit_tiny16_cls" | "vit_micro" | "vit_micro_cls" */
+                          "nf_regnet_tiny" | "vit_b16" | "vit_tiny16" | "vit_tiny16_cls" | "vit_micro" | "vit_micro_cls" |
+                          "clip_vit_b32" | "clip_vit_micro" | "clip_vit_nano" */
   int32_t batch;       /* pairs per inner step (mini_batch_size, distill.py:511)          */
   int32_t num_queries; /* rows of image_syn / text_syn (distill.py:630)                    */
   int32_t image_size;  /* square input, multiple of 32                                     */
@@ -70,7 +71,8 @@ const char* mdd_last_error(void);
  * mdd_op_contrastive refuses what its kernels cannot take; 12 = + mdd_op_image_edge, mdd_op_vit_glue, mdd_op_lin_pack,
  * mdd_op_resid, mdd_flat_dot / _scale_out / _sub_inplace / _lambda_init / _match_finalize / _d2f / _accum_f2d; 13 = +
  * in-engine dropout masks (mdd_iter_args.drop_p / drop_iteration / drop_seed, mdd_txt_forward_rng, mdd_op_dropout_mask,
- * mdd_sizeof_iter_args).  A binding built against another version must refuse to load. */
+ * mdd_sizeof_iter_args); still 13 (new symbols only, no struct changed): + mdd_op_quick_gelu / mdd_op_quick_gelu_bwd and the
+ * CLIP ViT variants.  A binding built against another version must refuse to load. */
 #define MDD_ABI_VERSION 13
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
@@ -476,6 +478,7 @@ int mdd_allreduce_syn_grads(mdd_comm* c, float* buf_dev, int64_t n, int average,
  *   layernorm_bwd  dx (+ `res` when non-NULL: the gradient arriving over the residual connection), and dgamma / dbeta
  *                  ACCUMULATED (+=, fp32 atomics) into the caller's zeroed/partial sums
  *   gelu           a = GELU(c) (exact, erf);  gelu_bwd  cbar = abar * GELU'(c)
+ *   quick_gelu     a = c * sigmoid(1.702 c) (CLIP's QuickGELU);  quick_gelu_bwd  cbar = abar * QuickGELU'(c)
  *   softmax        p = softmax(scale * s) over `cols` of each row (row stride ld); softmax_bwd  ds = scale*p*(dp - <p,dp>);
  *                  dtype = the storage type of the score tensors (the engine's bf16 mode keeps them in bf16: the matrix-core
  *                  contractions round them to bf16 anyway)
@@ -517,6 +520,9 @@ int mdd_op_layernorm_bwd(int dtype, int rows, int dim, float eps, const void* x,
 int mdd_op_gelu(int dtype, int64_t n, const void* c, const void* c_t, void* a, void* a_t, void* stream);
 int mdd_op_gelu_bwd(int dtype, int64_t n, const void* c, const void* c_t, const void* abar, const void* abar_t,
                     void* cbar, void* cbar_t, void* stream);
+int mdd_op_quick_gelu(int dtype, int64_t n, const void* c, const void* c_t, void* a, void* a_t, void* stream);
+int mdd_op_quick_gelu_bwd(int dtype, int64_t n, const void* c, const void* c_t, const void* abar, const void* abar_t,
+                          void* cbar, void* cbar_t, void* stream);
 int mdd_op_softmax(int dtype, int64_t rows, int cols, int ld, float scale, const void* s, const void* s_t, void* p,
                    void* p_t, void* stream);
 int mdd_op_softmax_bwd(int dtype, int64_t rows, int cols, int ld, float scale, const void* p, const void* p_t,

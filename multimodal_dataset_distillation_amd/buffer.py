@@ -57,7 +57,7 @@ def build_parser():
     p.add_argument("--k_test", type=int, default=128)
     p.add_argument("--load_npy", type=bool, default=False)
     p.add_argument("--image_encoder", type=str, default="nfnet",
-                   help="nfnet | vit | nf_resnet50 | nf_regnet (the reference's names) or an engine variant "
+                   help="nfnet | vit | nf_resnet50 | nf_regnet | clip (the reference's names) or an engine variant "
                         "(networks.VARIANTS)")
     p.add_argument("--text_encoder", type=str, default="bert", choices=["bert", "clip"])
     p.add_argument("--margin", default=0.2, type=float)

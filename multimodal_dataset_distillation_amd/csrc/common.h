@@ -142,6 +142,16 @@ DEVI Dual dsilu_(Dual x) {
   float s = sigmoidf_(x.v);
   return Dual(s * (1.f + x.v * (1.f - s)), s * (1.f - s) * (2.f + x.v * (1.f - 2.f * s)) * x.t);
 }
+// QuickGELU (CLIP's MLP activation) q(x) = x*sigmoid(a x), a = 1.702: q(x) = silu(a x)/a, so with u = a x, s = sigmoid(u):
+// q' = silu'(u) = s(1+u(1-s));  q'' = a*silu''(u) = a s(1-s)(2+u(1-2s))
+constexpr float QGELU_A = 1.702f;
+DEVI float qgelu_(float x) { return x * sigmoidf_(QGELU_A * x); }
+DEVI float dqgelu_(float x) { return dsilu_(QGELU_A * x); }
+DEVI Dual qgelu_(Dual x) { return Dual(qgelu_(x.v), dqgelu_(x.v) * x.t); }
+DEVI Dual dqgelu_(Dual x) {
+  const float u = QGELU_A * x.v, s = sigmoidf_(u);
+  return Dual(s * (1.f + u * (1.f - s)), QGELU_A * s * (1.f - s) * (2.f + u * (1.f - 2.f * s)) * x.t);
+}
 // exact (erf) GELU, as nn.GELU() default: g = x*Phi(x); g' = Phi + x*phi; g'' = phi*(2 - x^2)
 DEVI float gelu_(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 DEVI float dgelu_(float x) {

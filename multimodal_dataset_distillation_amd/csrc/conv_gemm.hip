@@ -20,6 +20,9 @@
 // ReLU epilogues (NF-ResNet, ConvEpi::act == 3) are instances of the same kernels compiled in a translation unit of
 // their own (conv_gemm_relu.hip includes this file with MDD_CONV_GEMM_RELU_TU defined): launch_conv_gemm hands such a
 // launch to launch_conv_gemm_relu.
+// QuickGELU epilogues (CLIP's MLP, ConvEpi::act == 4) follow the same precedent: conv_gemm_qgelu.hip includes this file with
+// MDD_CONV_GEMM_QGELU_TU defined and holds the 128 x 128 pointwise instances and the k_gemm_pipe instance of that
+// activation; launch_conv_gemm hands such a launch to launch_conv_gemm_qgelu.
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
@@ -174,15 +177,18 @@ DEVI void epi_wave_sync() {
 // (2 = the same GELU through the 1.5e-7 erf approximation: bf16 storage only, k_gemm_pipe), 3 = ReLU (NF-ResNet: its
 // derivative is the step 1[x > 0], its second derivative 0)
 template <int ACT> DEVI float actf(float x) {
-  if constexpr (ACT == 3) return relu_(x);
+  if constexpr (ACT == 4) return qgelu_(x);
+  else if constexpr (ACT == 3) return relu_(x);
   else if constexpr (ACT == 2) return gelu_fast_(x); else if constexpr (ACT == 1) return gelu_(x); else return silu_(x);
 }
 template <int ACT> DEVI float dactf(float x) {
-  if constexpr (ACT == 3) return x > 0.f ? 1.f : 0.f;
+  if constexpr (ACT == 4) return dqgelu_(x);
+  else if constexpr (ACT == 3) return x > 0.f ? 1.f : 0.f;
   else if constexpr (ACT == 2) return dgelu_fast_(x); else if constexpr (ACT == 1) return dgelu_(x); else return dsilu_(x);
 }
 template <int ACT> DEVI Dual dactf(Dual x) {
-  if constexpr (ACT == 3) return Dual(x.v > 0.f ? 1.f : 0.f, 0.f);
+  if constexpr (ACT == 4) return dqgelu_(x);
+  else if constexpr (ACT == 3) return Dual(x.v > 0.f ? 1.f : 0.f, 0.f);
   else if constexpr (ACT == 2) return dgelu_fast_(x); else if constexpr (ACT == 1) return dgelu_(x); else return dsilu_(x);
 }
 
@@ -624,8 +630,8 @@ DEVI void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
 template <int ACT_>
 __global__ __launch_bounds__(512, 1) void k_gemm_pipe(const KArgs p) {
   typedef bf16 AT;
-  // GELU, GELU', GELU'' from the 1.5e-7 erf approximation with one shared exponential
-  constexpr int ACT = ACT_ == 1 ? 2 : 0;
+  // GELU, GELU', GELU'' from the 1.5e-7 erf approximation with one shared exponential; ACT_ == 4: QuickGELU
+  constexpr int ACT = ACT_ == 1 ? 2 : (ACT_ == 4 ? 4 : 0);
   constexpr int TM = 4, TN = 2, MODE = 0, CE = 8, BM = 256;
   // the waves of a block run their epilogues independently (wave-private staging)
   constexpr bool IBK = false, EPI_WAVE_SYNC = true;
@@ -775,7 +781,12 @@ bool pipe_gemm_shape(const ConvGeom& g, int M) {
 // false = shape not taken (the caller goes on to the one-stage kernel)
 bool launch_pipe_gemm(const KArgs& a, hipStream_t st) {
   const ConvGeom& g = a.g;
-  if (!pipe_gemm_shape(g, a.M) || a.ep.ib != nullptr) return false;
+#ifdef MDD_CONV_GEMM_QGELU_TU
+  if (!pipe_gemm_shape(g, a.M) || a.ep.ib != nullptr || a.ep.act != 4) return false;
+#else
+  // (a QuickGELU launch belongs to the instance of conv_gemm_qgelu.hip: never the no-activation instance here)
+  if (!pipe_gemm_shape(g, a.M) || a.ep.ib != nullptr || a.ep.act == 4) return false;
+#endif
   KArgs k = a;
   k.mtiles = (a.M + 255) / 256;
   k.ntiles = (g.nc + 255) / 256;
@@ -785,14 +796,23 @@ bool launch_pipe_gemm(const KArgs& a, hipStream_t st) {
   (void)hipGetDevice(&dev);
   const uint64_t bit = 1ull << (dev & 63);
   if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
+#ifdef MDD_CONV_GEMM_QGELU_TU
+    if (hipFuncSetAttribute((const void*)k_gemm_pipe<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess)
+      return false;
+#else
     if (hipFuncSetAttribute((const void*)k_gemm_pipe<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_gemm_pipe<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess)
       return false;
+#endif
     attr_devs.fetch_or(bit, std::memory_order_release);
   }
   const unsigned blocks = (unsigned)(k.mtiles * k.ntiles);
+#ifdef MDD_CONV_GEMM_QGELU_TU
+  k_gemm_pipe<4><<<blocks, 512, 131072, st>>>(k);
+#else
   if (a.ep.act == 1) k_gemm_pipe<1><<<blocks, 512, 131072, st>>>(k);
   else k_gemm_pipe<0><<<blocks, 512, 131072, st>>>(k);
+#endif
   return true;
 }
 #endif  // MDD_CONV_GEMM_RELU_TU
@@ -850,6 +870,21 @@ void launch_conv_gemm_(const ConvGeom& g, const AT* A1, const AT* B1, const AT* 
   const bool kfull = ((g.k * g.k * g.kc) % Mma<AT>::KE) == 0;
   // per-image bias (ConvEpi::ib): pointwise data gradients with an activation epilogue only
   const bool ibk = ACTV == 0 && ep.ib != nullptr && mode == 0 && (ep.mode == EPI_BWD || ep.mode == EPI_BWD_T);
+#ifdef MDD_CONV_GEMM_QGELU_TU
+  // QuickGELU epilogues (CLIP's MLP): the k_gemm_pipe instance where the shape is its own, else the 128 x 128 pointwise
+  // kernel, as the exact-GELU launches of conv_gemm.hip choose; conv_gemm_supports_gelu() gates both activations
+  static_assert(ACTV == 4, "this translation unit holds the QuickGELU instances only");
+  (void)mode; (void)ibk;
+  if constexpr (sizeof(AT) == 2) {
+    if (launch_pipe_gemm(a, st)) return;
+  }
+  if constexpr (sizeof(AT) == 4) {
+    if (g.prec == 2 || g.prec == 3) { if (kfull) launch_cfg<AT, 2, 2, 2, 2, 0, true, 2, false, 4>(a, st); else launch_cfg<AT, 2, 2, 2, 2, 0, false, 2, false, 4>(a, st); return; }
+    if (g.prec == 1) { if (kfull) launch_cfg<AT, 2, 2, 2, 2, 0, true, 1, false, 4>(a, st); else launch_cfg<AT, 2, 2, 2, 2, 0, false, 1, false, 4>(a, st); return; }
+  }
+  if (kfull) launch_cfg<AT, 2, 2, 2, 2, 0, true, 0, false, 4>(a, st);
+  else launch_cfg<AT, 2, 2, 2, 2, 0, false, 0, false, 4>(a, st);
+#else
   if constexpr (sizeof(AT) == 2) {
     // MODE 4: 3x3 stride-1 "same" conv (forward or data gradient) whose group is one 128-byte channel row
     const bool slab = g.k == 3 && g.stride == 1 && g.pad == 1 && g.kc == 64 && g.nc <= 64 && g.ha == g.ho &&
@@ -905,14 +940,26 @@ void launch_conv_gemm_(const ConvGeom& g, const AT* A1, const AT* B1, const AT* 
   else MDD_DISPATCH(2, 2, 2, 2);                   // 128 x 128
 #undef MDD_DISPATCH
 #undef MDD_DISPATCH_P
+#endif  // MDD_CONV_GEMM_QGELU_TU
 }
 
 }  // namespace
 
-#ifndef MDD_CONV_GEMM_RELU_TU
+#if defined(MDD_CONV_GEMM_QGELU_TU)
+template <class AT>
+void launch_conv_gemm_qgelu(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
+                            const ConvEpi& ep, hipStream_t st) {
+  launch_conv_gemm_<AT, 4>(g, A1, B1, A2, B2, ep, st);
+}
+template void launch_conv_gemm_qgelu<float>(const ConvGeom&, const float*, const float*, const float*,
+                                            const float*, const ConvEpi&, hipStream_t);
+template void launch_conv_gemm_qgelu<bf16>(const ConvGeom&, const bf16*, const bf16*, const bf16*,
+                                           const bf16*, const ConvEpi&, hipStream_t);
+#elif !defined(MDD_CONV_GEMM_RELU_TU)
 template <class AT>
 void launch_conv_gemm(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
                       const ConvEpi& ep, hipStream_t st) {
+  if (ep.act == 4) { launch_conv_gemm_qgelu<AT>(g, A1, B1, A2, B2, ep, st); return; }
   if (ep.act == 3 && (ep.out_act || ep.mode == EPI_BWD_T)) { launch_conv_gemm_relu<AT>(g, A1, B1, A2, B2, ep, st); return; }
   if constexpr (sizeof(AT) == 2) {   // grouped 3x3 with 8 channels per group: csrc/conv_g8.hip where it is routed there
     if (g.k == 3 && g.kc == 8 && g.nc == 8 && launch_conv_g8(g, A1, B1, A2, B2, ep, st)) return;

@@ -134,7 +134,14 @@ bool get_cfg(const char* variant, NfCfg& c) {
 }
 
 // ViT topology (BASELINE configs[4]; timm 0.6.7 VisionTransformer as restated in oracle/vit_ref.py)
-struct VitCfg { int patch, dim, depth, heads; float eps; int head = 0; };   // head > 0: classifier Linear(dim, head)
+struct VitCfg {
+  int patch, dim, depth, heads; float eps; int head = 0;   // head > 0: classifier Linear(dim, head)
+  int act = 1;       // MLP activation (ConvEpi::act): 1 exact GELU, 4 QuickGELU
+  int pre_ln = 0;    // a LayerNorm on the embedded sequence in front of the first block (CLIP's ln_pre)
+  int pe_bias = 1;   // the patch convolution has a bias
+  int proj = 0;      // > 0: bias-free output projection of the normalised class token, stored [dim, proj] (features = x @ proj)
+  int naming = 0;    // parameter names and registration order: 0 timm VisionTransformer, 1 OpenAI clip (model.visual.*)
+};
 bool get_vit_cfg(const char* variant, VitCfg& c) {
   if (!strcmp(variant, "vit_b16")) { c = {16, 768, 12, 12, 1e-6f}; return true; }      // vit_base_patch16_224
   if (!strcmp(variant, "vit_tiny16")) { c = {16, 192, 12, 3, 1e-6f}; return true; }    // vit_tiny_patch16_224 (networks.py:668)
@@ -142,6 +149,13 @@ bool get_vit_cfg(const char* variant, VitCfg& c) {
   // the reference's 'vit' as it stands (networks.py:668: no num_classes=0): timm's 1000-way head stays on the model
   if (!strcmp(variant, "vit_tiny16_cls")) { c = {16, 192, 12, 3, 1e-6f, 1000}; return true; }
   if (!strcmp(variant, "vit_micro_cls")) { c = {8, 64, 2, 2, 1e-6f, 24}; return true; }
+  // OpenAI CLIP ViT-B/32 image tower (clip/model.py VisionTransformer(224, 32, 768, 12, 12, 512)); the reference's
+  // --image_encoder clip (networks.py:659-662) uses it through encode_image
+  if (!strcmp(variant, "clip_vit_b32")) { c = {32, 768, 12, 12, 1e-5f, 0, 4, 1, 0, 512, 1}; return true; }
+  // build-defined miniatures (tests): micro's MLP (256 wide) runs the fused QuickGELU epilogues, nano's (64 wide) the
+  // chunk kernels
+  if (!strcmp(variant, "clip_vit_micro")) { c = {8, 64, 2, 2, 1e-5f, 0, 4, 1, 0, 24, 1}; return true; }
+  if (!strcmp(variant, "clip_vit_nano")) { c = {8, 16, 2, 2, 1e-5f, 0, 4, 1, 0, 8, 1}; return true; }
   return false;
 }
 
@@ -217,12 +231,18 @@ template <class AT>
 struct Eng : mdd_engine {
   NfCfg nf;
   bool is_vit = false;     // the image encoder is a Vision Transformer (vit_forward / vit_backward below)
+  // bf16 storage of the CLIP tower: the class-token row of the residual stream is carried in fp32 beside the stream
+  // (cls_fix).  ln_pre renormalises that row, which holds no image yet, to unit variance, so the image's share of it (and of
+  // the features read from it) stays a few per cent; a bf16 rounding of the row at every residual sum is then as large as
+  // that share.  timm's towers start the row near 0 and keep the plain bf16 stream.
+  bool cls_hi = false;
   bool fused_attn = false; // bf16 ViT with head dimension 64 and <= 224 tokens: attention by attn.hip, no score-sized tensors
   VitCfg vit;
   int Tk = 0, sld = 0;     // tokens per image (1 + patches), row stride of the score / probability matrices
   std::vector<VitBlkL> vblk;
   int pe_conv = -1;
   int64_t off_cls = 0, off_pos = 0, off_nw = 0, off_nb = 0, off_hw = 0, off_hb = 0;
+  int64_t off_proj = 0, off_prew = 0, off_preb = 0;   // CLIP: output projection [dim, proj], ln_pre gain / bias
   int prec = 0;   // ConvGeom::prec of every contraction (fp32 storage: 0 exact, 1 split-bf16, 2 hi only)
   // fp32-storage engines: operand arithmetic of the image encoder's contractions per pass {F, B, T-F, T-B}
   // (0 = the engine's mode; mdd_engine_set_pass_precision -- the attribution table of DESIGN.md section 5)
@@ -275,6 +295,9 @@ struct Eng : mdd_engine {
   };
   struct ActSet {
     AT *VCOL = nullptr, *VPE = nullptr, *VCOLB = nullptr, *VPEB = nullptr;   // patch columns, patch embedding (+ grads)
+    AT *VE = nullptr, *VEB = nullptr;          // CLIP: the embedded sequence in front of ln_pre and its gradient
+    std::vector<float*> HC, HC2;               // cls_hi: the class-token row of X[l] / of X2 of layer l in fp32 [batch, dim]
+    float* HN = nullptr;                       // cls_hi: fp32 scratch of one LayerNorm over those rows
     AT *CLS = nullptr, *CLSN = nullptr, *CLSNB = nullptr, *CLSB = nullptr, *TMP = nullptr;
     float *hin = nullptr, *hinB = nullptr;     // classifier input / its gradient (fp32): the ViT's normalised class token,
                                                // the pooled features of NF-ResNet / NF-RegNet
@@ -365,17 +388,48 @@ struct Eng : mdd_engine {
       CHECK_ARG(D % vit.heads == 0 && Tk <= 512, "heads must divide dim; at most 512 tokens");
       // bf16: attention through csrc/attn.hip (scores never reach HBM)
       fused_attn = sizeof(AT) == 2 && attention_fused_supported(Tk, D / vit.heads);
-      auto add_lin = [&](const std::string& name, int cin, int cout, int tokens, bool conv_shape) {
+      cls_hi = sizeof(AT) == 2 && vit.pre_ln;
+      // a linear's weight and bias by their full names (an empty bias name: no bias, ConvL::off_b = -1)
+      auto add_lin2 = [&](const std::string& wname, const std::string& bname, int cin, int cout, int tokens, bool conv_shape) {
         ConvL L; L.cin = cin; L.cout = cout; L.k = 1; L.stride = 1; L.groups = 1; L.pad = 0;
         L.hin = 1; L.hout = 1; L.cin_pad = cin; L.tokens = tokens;
-        if (conv_shape) L.off_w = add_param(pimg, name + ".weight", {cout, 3, vit.patch, vit.patch});
-        else L.off_w = add_param(pimg, name + ".weight", {cout, cin});
-        L.off_b = add_param(pimg, name + ".bias", {cout});
+        if (conv_shape) L.off_w = add_param(pimg, wname, {cout, 3, vit.patch, vit.patch});
+        else L.off_w = add_param(pimg, wname, {cout, cin});
+        L.off_b = bname.empty() ? -1 : add_param(pimg, bname, {cout});
         L.off_g = -1;
         L.off_p = packed_total; packed_total += L.packed();
         convs.push_back(L);
         return (int)convs.size() - 1;
       };
+      auto add_lin = [&](const std::string& name, int cin, int cout, int tokens, bool conv_shape) {
+        return add_lin2(name + ".weight", name + ".bias", cin, cout, tokens, conv_shape);
+      };
+      if (vit.naming == 1) {
+        // OpenAI clip VisionTransformer, flattened as reparam_module.py does (a module's own parameters, then its children
+        // in registration order): class_embedding, positional_embedding, proj | conv1 (no bias) | ln_pre |
+        // transformer.resblocks.i.{attn (nn.MultiheadAttention: in_proj_weight, in_proj_bias, out_proj), ln_1,
+        // mlp.c_fc, mlp.c_proj, ln_2} | ln_post.  in_proj's rows are q | k | v with a head's channels adjacent: timm's qkv
+        CHECK_ARG(vit.proj > 0 && vit.pre_ln && !vit.pe_bias && vit.head == 0, "internal: the clip naming scheme is CLIP's tower");
+        const std::string v = "model.visual.";
+        off_cls = add_param(pimg, v + "class_embedding", {D});
+        off_pos = add_param(pimg, v + "positional_embedding", {Tk, D});
+        off_proj = add_param(pimg, v + "proj", {D, vit.proj});
+        pe_conv = add_lin2(v + "conv1.weight", "", 3 * vit.patch * vit.patch, D, Tk - 1, true);
+        off_prew = add_param(pimg, v + "ln_pre.weight", {D}); off_preb = add_param(pimg, v + "ln_pre.bias", {D});
+        for (int l = 0; l < vit.depth; ++l) {
+          const std::string pre = v + "transformer.resblocks." + std::to_string(l);
+          VitBlkL B;
+          B.qkv = add_lin2(pre + ".attn.in_proj_weight", pre + ".attn.in_proj_bias", D, 3 * D, Tk, false);
+          B.proj = add_lin(pre + ".attn.out_proj", D, D, Tk, false);
+          B.ln1_w = add_param(pimg, pre + ".ln_1.weight", {D}); B.ln1_b = add_param(pimg, pre + ".ln_1.bias", {D});
+          B.fc1 = add_lin(pre + ".mlp.c_fc", D, 4 * D, Tk, false);
+          B.fc2 = add_lin(pre + ".mlp.c_proj", 4 * D, D, Tk, false);
+          B.ln2_w = add_param(pimg, pre + ".ln_2.weight", {D}); B.ln2_b = add_param(pimg, pre + ".ln_2.bias", {D});
+          vblk.push_back(B);
+        }
+        off_nw = add_param(pimg, v + "ln_post.weight", {D}); off_nb = add_param(pimg, v + "ln_post.bias", {D});
+      } else {
+      CHECK_ARG(vit.proj == 0 && !vit.pre_ln && vit.pe_bias, "internal: timm naming has no ln_pre / projection");
       off_cls = add_param(pimg, "model.cls_token", {1, 1, D});
       off_pos = add_param(pimg, "model.pos_embed", {1, Tk, D});
       pe_conv = add_lin("model.patch_embed.proj", 3 * vit.patch * vit.patch, D, Tk - 1, true);
@@ -394,10 +448,11 @@ struct Eng : mdd_engine {
       if (vit.head > 0) {
         off_hw = add_param(pimg, "model.head.weight", {vit.head, D}); off_hb = add_param(pimg, "model.head.bias", {vit.head});
       }
+      }   // timm naming
       int ce = 16 / (int)sizeof(AT);
       CHECK_ARG(D % ce == 0 && (3 * vit.patch * vit.patch) % ce == 0 && (D / vit.heads) % 4 == 0,
                 "dims must be multiples of the 16-byte chunk");
-      P_img = off; feat = vit.head > 0 ? vit.head : D;
+      P_img = off; feat = vit.head > 0 ? vit.head : (vit.proj > 0 ? vit.proj : D);
       stem[0] = stem[1] = stem[2] = stem[3] = fin = -1;
       for (auto& L : convs) {
         LinPackDesc d; d.off_w = L.off_w; d.off_p = L.off_p; d.out = L.cout; d.in = L.cin; d.tile_start = lpd_tiles; d.pad_ = 0;
@@ -533,6 +588,14 @@ struct Eng : mdd_engine {
     const int64_t pr = n * vit.heads * Tk * sld;
     plan(&s.VCOL, n * np * kk, "vit.COL", slot); plan(&s.VPE, n * np * D, "vit.PE", slot);
     plan(&s.VCOLB, n * np * kk, "vit.COLB", slot); plan(&s.VPEB, n * np * D, "vit.PEB", slot);
+    s.VE = s.VEB = nullptr;
+    if (vit.pre_ln) { plan(&s.VE, M * D, "vit.E", slot); plan(&s.VEB, M * D, "vit.EB", slot); }   // ln_pre's input, its gradient
+    if (cls_hi) {
+      s.HC.resize(vit.depth + 1); s.HC2.resize(vit.depth);
+      for (int l = 0; l <= vit.depth; ++l) plan(&s.HC[l], n * D, nullptr, slot);
+      for (int l = 0; l < vit.depth; ++l) plan(&s.HC2[l], n * D, nullptr, slot);
+      plan(&s.HN, n * D, nullptr, slot);
+    }
     plan(&s.CLS, n * D, "vit.CLS", slot); plan(&s.CLSN, n * D, "vit.CLSN", slot);
     plan(&s.CLSNB, n * D, "vit.CLSNB", slot); plan(&s.CLSB, n * D, "vit.CLSB", slot);
     plan(&s.TMP, M * D, "vit.TMP", slot);
@@ -917,10 +980,10 @@ struct Eng : mdd_engine {
     ConvEpi e; memset(&e, 0, sizeof e);
     e.beta = beta; e.act = act;
     if (!T) {
-      e.mode = EPI_FWD; e.bias = th + L.off_b; e.out_raw = C; e.out_act = A;
+      e.mode = EPI_FWD; e.bias = L.off_b >= 0 ? th + L.off_b : nullptr; e.out_raw = C; e.out_act = A;
       gemm(L, g, in, wf + L.off_p, nullptr, nullptr, e, st);
     } else {
-      e.mode = EPI_FWD_T; e.bias_t = th_t + L.off_b; e.out_raw = C_t; e.out_act = A_t; e.c = C;
+      e.mode = EPI_FWD_T; e.bias_t = L.off_b >= 0 ? th_t + L.off_b : nullptr; e.out_raw = C_t; e.out_act = A_t; e.c = C;
       if (in_t) gemm(L, g, in_t, wf + L.off_p, in, wf_t + L.off_p, e, st);
       else gemm(L, g, in, wf_t + L.off_p, nullptr, nullptr, e, st);
     }
@@ -971,19 +1034,20 @@ struct Eng : mdd_engine {
   void conv_bwd_w(bool T, const ConvL& L, const AT* dy, const AT* dy_t, const AT* x, const AT* x_t,
                   float* dwf_, float* dwf_t_, float* gout, hipStream_t) {
     const ConvL* Lp = &L;
+    float* const dbias = L.off_b >= 0 ? gout + L.off_b : nullptr;   // a bias-free layer (CLIP's conv1): no bias gradient
     // the wide pointwise layers queued between two flushes share one weight-gradient launch
     if (sizeof(AT) == 2 && !prof_on && conv_wgrad_group_takes(gfwd(L))) {
       WgQ q; q.L = Lp; q.it.g = gfwd(L);
       if (!T) { q.it.dy1 = dy; q.it.x1 = x; q.it.dy2 = nullptr; q.it.x2 = nullptr; q.it.dW = dwf_ + L.off_p; }
       else { q.it.dy1 = dy_t; q.it.x1 = x; q.it.dy2 = x_t ? dy : nullptr; q.it.x2 = x_t; q.it.dW = dwf_t_ + L.off_p; }
-      q.it.dbias = gout + L.off_b;
+      q.it.dbias = dbias;
       wgroup.push_back(q);
       return;
     }
     wq.push_back([=](hipStream_t ws_) {
       ConvGeom g = gfwd(*Lp);
-      if (!T) wgrad(*Lp, g, dy, x, nullptr, nullptr, dwf_ + Lp->off_p, gout + Lp->off_b, ws_);
-      else wgrad(*Lp, g, dy_t, x, x_t ? dy : nullptr, x_t, dwf_t_ + Lp->off_p, gout + Lp->off_b, ws_);
+      if (!T) wgrad(*Lp, g, dy, x, nullptr, nullptr, dwf_ + Lp->off_p, dbias, ws_);
+      else wgrad(*Lp, g, dy_t, x, x_t ? dy : nullptr, x_t, dwf_t_ + Lp->off_p, dbias, ws_);
     });
   }
   // data gradient of conv L with fused epilogue
@@ -1051,6 +1115,21 @@ struct Eng : mdd_engine {
     return a;
   }
 #define VIT_RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+  // cls_hi: one residual sum of the class-token rows in fp32, h = h_prev + (the branch output's class rows), the LayerNorm
+  // that follows it (gain / bias at gw / gb; gw < 0: none) from the fp32 rows, and both written over what the bf16 kernels
+  // left in the class rows of the LayerNorm's output and of the stream.  Tangent call: the same on the tangents, the
+  // LayerNorm's tangent from the stashed fp32 primal rows.
+  int cls_fix(bool T, ActSet& P, ActSet& Q, float* hp, float* hq, const float* hp_prev, const float* hq_prev, const AT* tmp_p,
+              const AT* tmp_q, int64_t gw, int64_t gb, AT* n_p, AT* n_q, AT* x_p, AT* x_q, const float* th, const float* th_t,
+              hipStream_t st) {
+    const int D = vit.dim;
+    launch_cls_axpy_f32<AT>(T ? hq : hp, T ? hq_prev : hp_prev, T ? tmp_q : tmp_p, N, Tk, D, st);
+    if (gw >= 0)
+      VIT_RC(mdd_op_layernorm(MDD_DTYPE_F32, N, D, vit.eps, hp, T ? hq : nullptr, th + gw, tp(T, th_t + gw), th + gb,
+                              tp(T, th_t + gb), P.HN, T ? Q.HN : nullptr, st));
+    launch_cls_put<AT>(gw >= 0 ? (T ? n_q : n_p) : nullptr, T ? Q.HN : P.HN, T ? x_q : x_p, T ? hq : hp, N, Tk, D, st);
+    return 0;
+  }
   int vit_forward(bool T, int slot, const float* th, const float* th_t, const float* image, const int64_t* idx,
                   float* feat_out, hipStream_t st) {
     ActSet& P = sets[slot]; ActSet& Q = tn;
@@ -1061,8 +1140,13 @@ struct Eng : mdd_engine {
     pack_weights(T, th, th_t, st);
     if (!T) launch_patchify<AT>(P.VCOL, image, idx, N, S, vit.patch, st);
     conv_fwd(T, convs[pe_conv], P.VCOL, nullptr, P.VPE, Q.VPE, nullptr, nullptr, 1.f, th, th_t, st);
-    launch_vit_embed<AT>(P.X[0], T ? Q.X[0] : nullptr, P.VPE, T ? Q.VPE : nullptr, th + off_cls,
-                         tp(T, th_t + off_cls), th + off_pos, tp(T, th_t + off_pos), N, Tk, D, st);
+    // the embedded sequence is the stream, or (CLIP) the stashed input E of ln_pre: X[0] = LN(E)
+    launch_vit_embed<AT>(vit.pre_ln ? P.VE : P.X[0], T ? (vit.pre_ln ? Q.VE : Q.X[0]) : nullptr, P.VPE, T ? Q.VPE : nullptr,
+                         th + off_cls, tp(T, th_t + off_cls), th + off_pos, tp(T, th_t + off_pos), N, Tk, D, st);
+    if (vit.pre_ln)
+      VIT_RC(mdd_op_layernorm(VDT, M, D, vit.eps, P.VE, T ? Q.VE : nullptr, th + off_prew, tp(T, th_t + off_prew),
+                              th + off_preb, tp(T, th_t + off_preb), P.X[0], T ? Q.X[0] : nullptr, st));
+    if (cls_hi) launch_cls_axpy_f32<AT>(T ? Q.HC[0] : P.HC[0], nullptr, T ? Q.X[0] : P.X[0], N, Tk, D, st);
     for (int l = 0; l < vit.depth; ++l) {
       const VitBlkL& B = vblk[l]; VitActs& pa = P.vb[l]; VitActs& qa = Q.vb[l];
       const AT *x = P.X[l], *x_t = T ? Q.X[l] : nullptr;
@@ -1072,6 +1156,8 @@ struct Eng : mdd_engine {
         VIT_RC(mdd_op_add_layernorm(VDT, M, D, vit.eps, pp.X2, T ? qp.X2 : nullptr, P.TMP, T ? Q.TMP : nullptr, P.X[l],
                                     T ? Q.X[l] : nullptr, th + B.ln1_w, tp(T, th_t + B.ln1_w), th + B.ln1_b, tp(T, th_t + B.ln1_b),
                                     pa.N1, T ? qa.N1 : nullptr, st));
+        if (cls_hi) VIT_RC(cls_fix(T, P, Q, P.HC[l], Q.HC[l], P.HC2[l - 1], Q.HC2[l - 1], P.TMP, Q.TMP, B.ln1_w, B.ln1_b, pa.N1,
+                                   qa.N1, P.X[l], Q.X[l], th, th_t, st));
       } else {
         VIT_RC(mdd_op_layernorm(VDT, M, D, vit.eps, x, x_t, th + B.ln1_w, tp(T, th_t + B.ln1_w), th + B.ln1_b,
                                 tp(T, th_t + B.ln1_b), pa.N1, T ? qa.N1 : nullptr, st));
@@ -1102,18 +1188,34 @@ struct Eng : mdd_engine {
       VIT_RC(mdd_op_add_layernorm(VDT, M, D, vit.eps, x, x_t, P.TMP, T ? Q.TMP : nullptr, pa.X2, T ? qa.X2 : nullptr,
                                   th + B.ln2_w, tp(T, th_t + B.ln2_w), th + B.ln2_b, tp(T, th_t + B.ln2_b), pa.N2,
                                   T ? qa.N2 : nullptr, st));
-      // fc1 with the exact GELU in its epilogue (C and A = gelu(C) written by the contraction; tangent: C_t and
-      // A_t = gelu'(C) C_t) wherever the GELU instance of the kernel exists for this width
+      if (cls_hi) VIT_RC(cls_fix(T, P, Q, P.HC2[l], Q.HC2[l], P.HC[l], Q.HC[l], P.TMP, Q.TMP, B.ln2_w, B.ln2_b, pa.N2, qa.N2,
+                                 pa.X2, qa.X2, th, th_t, st));
+      // fc1 with the exact GELU (CLIP: QuickGELU) in its epilogue (C and A = gelu(C) written by the contraction; tangent:
+      // C_t and A_t = gelu'(C) C_t) wherever the GELU instance of the kernel exists for this width
       if (conv_gemm_supports_gelu(gfwd(convs[B.fc1]))) {
-        conv_fwd(T, convs[B.fc1], pa.N2, qa.N2, pa.C, qa.C, pa.A, qa.A, 1.f, th, th_t, st, 1);
+        conv_fwd(T, convs[B.fc1], pa.N2, qa.N2, pa.C, qa.C, pa.A, qa.A, 1.f, th, th_t, st, vit.act);
       } else {
         conv_fwd(T, convs[B.fc1], pa.N2, qa.N2, pa.C, qa.C, nullptr, nullptr, 1.f, th, th_t, st);
-        VIT_RC(mdd_op_gelu(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, pa.A, T ? qa.A : nullptr, st));
+        if (vit.act == 4) VIT_RC(mdd_op_quick_gelu(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, pa.A, T ? qa.A : nullptr, st));
+        else VIT_RC(mdd_op_gelu(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, pa.A, T ? qa.A : nullptr, st));
       }
       conv_fwd(T, convs[B.fc2], pa.A, qa.A, P.TMP, Q.TMP, nullptr, nullptr, 1.f, th, th_t, st);
       if (l + 1 == vit.depth)    // otherwise formed by the next layer's first LayerNorm
         launch_add2<AT>(P.X[l + 1], T ? Q.X[l + 1] : nullptr, pa.X2, T ? qa.X2 : nullptr, P.TMP, T ? Q.TMP : nullptr,
                         (int64_t)M * D, st);
+      if (cls_hi && l + 1 == vit.depth)
+        VIT_RC(cls_fix(T, P, Q, P.HC[l + 1], Q.HC[l + 1], P.HC2[l], Q.HC2[l], P.TMP, Q.TMP, -1, -1, nullptr, nullptr,
+                       P.X[l + 1], Q.X[l + 1], th, th_t, st));
+    }
+    if (cls_hi) {
+      // features = LN_post(class row) @ proj, the LayerNorm in fp32 from the fp32 row straight into the projection's input
+      VIT_RC(mdd_op_layernorm(MDD_DTYPE_F32, N, D, vit.eps, P.HC[vit.depth], T ? Q.HC[vit.depth] : nullptr, th + off_nw,
+                              tp(T, th_t + off_nw), th + off_nb, tp(T, th_t + off_nb), P.hin, T ? Q.hin : nullptr, st));
+      launch_linear_dgrad(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_proj, tp(T, th_t + off_proj),
+                          nullptr, N, vit.proj, D, lin_main, st);
+      VIT_RC(copy_features(T, P, feat_out, st));
+      POST_WALK();
+      return 0;
     }
     // feature = LayerNorm(x_L)[:, 0]: normalise the class rows only
     launch_cls_gather<AT>(T ? Q.CLS : P.CLS, T ? Q.X[vit.depth] : P.X[vit.depth], N, Tk, D, st);
@@ -1123,6 +1225,12 @@ struct Eng : mdd_engine {
       // classifier head on the normalised class token (timm default; reference networks.py:668): small-batch fp32 linear
       launch_act_to_f32<AT>(T ? Q.hin : P.hin, T ? Q.CLSN : P.CLSN, (int64_t)N * D, st);
       classifier_fwd(T, P, Q, D, vit.head, th, th_t, feat_out, st);
+    } else if (vit.proj > 0) {
+      // CLIP: features = LN_post(cls) @ proj, proj stored [dim, proj] -- the small-batch linears with the roles swapped:
+      // the data-gradient form A W of a row-major [contract, out] matrix is this forward (no bias, no mask)
+      launch_act_to_f32<AT>(T ? Q.hin : P.hin, T ? Q.CLSN : P.CLSN, (int64_t)N * D, st);
+      launch_linear_dgrad(P.y, T ? feat_out : nullptr, P.hin, T ? Q.hin : nullptr, th + off_proj, tp(T, th_t + off_proj),
+                          nullptr, N, vit.proj, D, lin_main, st);
     } else {
       launch_act_to_f32<AT>(T ? feat_out : P.y, T ? Q.CLSN : P.CLSN, (int64_t)N * D, st);
     }
@@ -1146,8 +1254,22 @@ struct Eng : mdd_engine {
     if (vit.head > 0) {
       classifier_bwd(T, P, Q, O, D, vit.head, ybar_t_in, gout, th, th_t, st);
       launch_f32_to_act<AT>(T ? Q.CLSNB : O.CLSNB, T ? Q.hinB : O.hinB, (int64_t)N * D, st);
+    } else if (vit.proj > 0) {
+      // dproj [dim, proj] = hin^T ybar (the weight-gradient form with its operands exchanged, no bias gradient);
+      // dhin = ybar proj^T (the forward form)
+      launch_linear_wgrad(gout + off_proj, nullptr, P.hin, T ? Q.hin : nullptr, O.yB, T ? ybar_t_in : nullptr, N, vit.proj, D,
+                          lin_main, st);
+      launch_linear_fwd(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_proj, tp(T, th_t + off_proj),
+                        nullptr, nullptr, N, vit.proj, D, 0, lin_main, st);
+      if (!cls_hi) launch_f32_to_act<AT>(T ? Q.CLSNB : O.CLSNB, T ? Q.hinB : O.hinB, (int64_t)N * D, st);
     } else
     launch_f32_to_act<AT>(T ? Q.CLSNB : O.CLSNB, T ? ybar_t_in : O.yB, (int64_t)N * D, st);
+    if (cls_hi) {   // LN_post's backward in fp32 on the fp32 class row, then into the stream's storage type
+      VIT_RC(mdd_op_layernorm_bwd(MDD_DTYPE_F32, N, D, vit.eps, P.HC[L_], T ? Q.HC[L_] : nullptr, O.hinB, T ? Q.hinB : nullptr,
+                                  th + off_nw, tp(T, th_t + off_nw), nullptr, nullptr, T ? nullptr : O.HN,
+                                  T ? Q.HN : nullptr, gp(off_nw), gt(off_nw), gp(off_nb), gt(off_nb), st));
+      launch_f32_to_act<AT>(T ? Q.CLSB : O.CLSB, T ? Q.HN : O.HN, (int64_t)N * D, st);
+    } else
     VIT_RC(mdd_op_layernorm_bwd(VDT, N, D, vit.eps, P.CLS, T ? Q.CLS : nullptr, O.CLSNB, T ? Q.CLSNB : nullptr,
                                 th + off_nw, tp(T, th_t + off_nw), nullptr, nullptr, T ? nullptr : O.CLSB,
                                 T ? Q.CLSB : nullptr, gp(off_nw), gt(off_nw), gp(off_nb), gt(off_nb), st));
@@ -1160,11 +1282,13 @@ struct Eng : mdd_engine {
       if (conv_gemm_supports_gelu(gdgrad(convs[B.fc2]))) {
         // fc2's data gradient with the GELU chain rule in its epilogue: raw AB (stashed: the tangent pass needs it)
         // and CB = gelu'(C) AB; tangent: CB_t = (gelu'(Dual(C, C_t)) Dual(AB, AB_t)).t from the stashed C, C_t, AB
-        conv_bwd_d(T, convs[B.fc2], xb, xb_t, epi_act(T, oa.AB, oa.CB, qa.CB, pa.C, qa.C, 1.f, nullptr, nullptr, 1), st);
+        conv_bwd_d(T, convs[B.fc2], xb, xb_t, epi_act(T, oa.AB, oa.CB, qa.CB, pa.C, qa.C, 1.f, nullptr, nullptr, vit.act), st);
       } else {
         conv_bwd_d(T, convs[B.fc2], xb, xb_t, epi_lin(T ? qa.AB : oa.AB, nullptr), st);
-        VIT_RC(mdd_op_gelu_bwd(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, oa.AB, T ? qa.AB : nullptr,
-                               T ? nullptr : oa.CB, T ? qa.CB : nullptr, st));
+        if (vit.act == 4) VIT_RC(mdd_op_quick_gelu_bwd(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, oa.AB, T ? qa.AB : nullptr,
+                                                       T ? nullptr : oa.CB, T ? qa.CB : nullptr, st));
+        else VIT_RC(mdd_op_gelu_bwd(VDT, (int64_t)M * 4 * D, pa.C, T ? qa.C : nullptr, oa.AB, T ? qa.AB : nullptr,
+                                    T ? nullptr : oa.CB, T ? qa.CB : nullptr, st));
       }
       lin_bwd_w(T, convs[B.fc1], oa.CB, qa.CB, pa.N2, qa.N2, gout, st);
       conv_bwd_d(T, convs[B.fc1], oa.CB, qa.CB, epi_lin(T ? qa.N2B : oa.N2B, nullptr), st);
@@ -1220,7 +1344,14 @@ struct Eng : mdd_engine {
                                   gp(B.ln1_b), gt(B.ln1_b), st));
       flush_w(st);
     }
-    launch_vit_embed_bwd<AT>(O.XB[0], T ? Q.XB[0] : nullptr, T ? nullptr : O.VPEB, T ? Q.VPEB : nullptr,
+    const AT *eb = O.XB[0], *eb_t = Q.XB[0];
+    if (vit.pre_ln) {   // CLIP: back through ln_pre (its gain / bias gradients), from the stashed embedded sequence
+      VIT_RC(mdd_op_layernorm_bwd(VDT, M, D, vit.eps, P.VE, T ? Q.VE : nullptr, O.XB[0], T ? Q.XB[0] : nullptr,
+                                  th + off_prew, tp(T, th_t + off_prew), nullptr, nullptr, T ? nullptr : O.VEB,
+                                  T ? Q.VEB : nullptr, gp(off_prew), gt(off_prew), gp(off_preb), gt(off_preb), st));
+      eb = O.VEB; eb_t = Q.VEB;
+    }
+    launch_vit_embed_bwd<AT>(eb, T ? eb_t : nullptr, T ? nullptr : O.VPEB, T ? Q.VPEB : nullptr,
                              gout + off_cls, gout + off_pos, N, Tk, D, st);
     lin_bwd_w(T, convs[pe_conv], O.VPEB, Q.VPEB, P.VCOL, nullptr, gout, st);
     if (dimage) {

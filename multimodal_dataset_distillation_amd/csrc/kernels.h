@@ -68,7 +68,8 @@ struct ConvEpi {
   const float* ib_t;
   float ib_mul;
   int ib_hw;
-  int act;                // activation of the fused chain rule: 0 SiLU, 1 exact GELU (conv_gemm_supports_gelu), 3 ReLU
+  int act;                // activation of the fused chain rule: 0 SiLU, 1 exact GELU (conv_gemm_supports_gelu), 3 ReLU,
+                          // 4 QuickGELU (same gate as the exact GELU)
   // squeeze-excite apply modes (EPI_FWD_SE / _T, conv_gemm_supports_se): x' (or its tangent) goes to out_x; the gate is
   // ib / ib_t ([nimg, co_tot] fp32, image = m / ib_hw), ga is ib_mul, the shortcut is add1 and its tangent add2
   void* out_x;            // AT*
@@ -106,6 +107,10 @@ bool conv_gemm_supports_se(const ConvGeom& g, int esize);
 template <class AT>
 void launch_conv_gemm_relu(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
                            const ConvEpi& ep, hipStream_t st);
+// ConvEpi::act == 4 (QuickGELU): the instances of conv_gemm_qgelu.hip; launch_conv_gemm forwards such launches itself
+template <class AT>
+void launch_conv_gemm_qgelu(const ConvGeom& g, const AT* A1, const AT* B1, const AT* A2, const AT* B2,
+                            const ConvEpi& ep, hipStream_t st);
 // the 256 x 256 pipelined kernels (k_gemm_pipe, k_wgrad_pipe) may be switched off at run time: the parity tests compare
 // an iteration with and without them (mdd_set_pipe_kernels)
 bool pipe_kernels_enabled();
@@ -337,6 +342,10 @@ template <class AT> void launch_add2(AT* o, AT* o_t, const AT* a, const AT* a_t,
                                      hipStream_t st);
 template <class AT> void launch_cls_gather(AT* out, const AT* x, int n, int tok, int dim, hipStream_t st);
 template <class AT> void launch_cls_scatter(AT* xb, const AT* in, int n, int tok, int dim, hipStream_t st);
+// class-token rows in fp32 beside the stream: h_out [n, dim] = h_in (0 when null) + x[:, token 0, :]; and back: the class
+// rows of a (and of b, when given) are overwritten with fa (fb)
+template <class AT> void launch_cls_axpy_f32(float* h_out, const float* h_in, const AT* x, int n, int tok, int dim, hipStream_t st);
+template <class AT> void launch_cls_put(AT* a, const float* fa, AT* b, const float* fb, int n, int tok, int dim, hipStream_t st);
 template <class AT> void launch_act_to_f32(float* o, const AT* a, int64_t n, hipStream_t st);
 template <class AT> void launch_f32_to_act(AT* o, const float* a, int64_t n, hipStream_t st);
 struct LinPackDesc { int64_t off_w, off_p; int out, in, tile_start, pad_; };

@@ -260,6 +260,33 @@ __global__ void k_gelu_bwd(const AT* __restrict__ c, const AT* __restrict__ c_t,
   }
 }
 
+// ------------------------------------------------------------------ QuickGELU x*sigmoid(1.702 x) on chunks (CLIP's MLP)
+template <class S, class AT>
+__global__ void k_quick_gelu_fwd(const AT* __restrict__ c, const AT* __restrict__ c_t, AT* __restrict__ a,
+                                 AT* __restrict__ a_t, int64_t chunks) {
+  constexpr int CE = Chunk<AT>::N;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < chunks; i += (int64_t)gridDim.x * blockDim.x) {
+    S x[CE], o[CE];
+    ldcS<S, AT>(c, c_t, i, x);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) o[e] = qgelu_(x[e]);
+    stcS<S, AT>(a, a_t, i, o);
+  }
+}
+template <class S, class AT>
+__global__ void k_quick_gelu_bwd(const AT* __restrict__ c, const AT* __restrict__ c_t, const AT* __restrict__ ab,
+                                 const AT* __restrict__ ab_t, AT* __restrict__ cb, AT* __restrict__ cb_t, int64_t chunks) {
+  constexpr int CE = Chunk<AT>::N;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < chunks; i += (int64_t)gridDim.x * blockDim.x) {
+    S x[CE], g[CE], o[CE];
+    ldcS<S, AT>(c, c_t, i, x);
+    ldcS<S, AT>(ab, ab_t, i, g);
+#pragma unroll
+    for (int e = 0; e < CE; ++e) o[e] = g[e] * dqgelu_(x[e]);
+    stcS<S, AT>(cb, cb_t, i, o);
+  }
+}
+
 // ------------------------------------------------------------------ softmax over rows of fp32 scores (a wave per row)
 constexpr int SM_MAXE = 8;     // columns per lane: cols <= 512
 template <class S, class TS>
@@ -493,6 +520,27 @@ __global__ void k_cls_scatter(AT* __restrict__ xb, const AT* __restrict__ in, in
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int t = (int)((i / dim) % tok);
     xb[i] = t == 0 ? in[(i / ((int64_t)tok * dim)) * dim + (i % dim)] : from_f<AT>(0.f);
+  }
+}
+// class-token rows in fp32 beside a bf16 stream (CLIP tower, engine.hip cls_fix): h_out[n, :] = h_in[n, :] (0 when null) +
+// x[n, token 0, :], and the way back: the class rows of a (and b, optional) are overwritten with fa (fb)
+template <class AT>
+__global__ void k_cls_axpy_f32(float* __restrict__ h_out, const float* __restrict__ h_in, const AT* __restrict__ x, int n,
+                               int tok, int dim) {
+  const int64_t total = (int64_t)n * dim;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t img = i / dim, d = i - img * dim;
+    h_out[i] = (h_in ? h_in[i] : 0.f) + to_f(x[img * tok * dim + d]);
+  }
+}
+template <class AT>
+__global__ void k_cls_put(AT* __restrict__ a, const float* __restrict__ fa, AT* __restrict__ b, const float* __restrict__ fb,
+                          int n, int tok, int dim) {
+  const int64_t total = (int64_t)n * dim;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t img = i / dim, d = i - img * dim;
+    if (a) a[img * tok * dim + d] = from_f<AT>(fa[i]);
+    if (b) b[img * tok * dim + d] = from_f<AT>(fb[i]);
   }
 }
 template <class AT> __global__ void k_act_to_f32(float* __restrict__ o, const AT* __restrict__ a, int64_t n) {
@@ -835,6 +883,12 @@ template <class AT> void launch_cls_gather(AT* out, const AT* x, int n, int tok,
 template <class AT> void launch_cls_scatter(AT* xb, const AT* in, int n, int tok, int dim, hipStream_t st) {
   k_cls_scatter<AT><<<vgrid((int64_t)n * tok * dim), 256, 0, st>>>(xb, in, n, tok, dim);
 }
+template <class AT> void launch_cls_axpy_f32(float* h_out, const float* h_in, const AT* x, int n, int tok, int dim, hipStream_t st) {
+  k_cls_axpy_f32<AT><<<vgrid((int64_t)n * dim), 256, 0, st>>>(h_out, h_in, x, n, tok, dim);
+}
+template <class AT> void launch_cls_put(AT* a, const float* fa, AT* b, const float* fb, int n, int tok, int dim, hipStream_t st) {
+  k_cls_put<AT><<<vgrid((int64_t)n * dim), 256, 0, st>>>(a, fa, b, fb, n, tok, dim);
+}
 template <class AT> void launch_act_to_f32(float* o, const AT* a, int64_t n, hipStream_t st) {
   k_act_to_f32<AT><<<vgrid(n), 256, 0, st>>>(o, a, n);
 }
@@ -917,6 +971,8 @@ void launch_lin_pack_all(const LinPackDesc* descs, int nd, int total_tiles, cons
   template void launch_add2<AT>(AT*, AT*, const AT*, const AT*, const AT*, const AT*, int64_t, hipStream_t);       \
   template void launch_cls_gather<AT>(AT*, const AT*, int, int, int, hipStream_t);                                \
   template void launch_cls_scatter<AT>(AT*, const AT*, int, int, int, hipStream_t);                               \
+  template void launch_cls_axpy_f32<AT>(float*, const float*, const AT*, int, int, int, hipStream_t);             \
+  template void launch_cls_put<AT>(AT*, const float*, AT*, const float*, int, int, int, hipStream_t);             \
   template void launch_act_to_f32<AT>(float*, const AT*, int64_t, hipStream_t);                                   \
   template void launch_f32_to_act<AT>(AT*, const float*, int64_t, hipStream_t);                                   \
   template void launch_lin_pack_all<AT>(const LinPackDesc*, int, int, const float*, const float*, AT*, AT*, AT*, AT*, \
@@ -1011,6 +1067,45 @@ int mdd_op_gelu_bwd(int dtype, int64_t n, const void* c, const void* c_t, const 
   } else {
     if (T) k_gelu_bwd<Dual, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, (const bf16*)c_t, (const bf16*)abar, (const bf16*)abar_t, (bf16*)cbar, (bf16*)cbar_t, ch);
     else k_gelu_bwd<float, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, nullptr, (const bf16*)abar, nullptr, (bf16*)cbar, nullptr, ch);
+  }
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+int mdd_op_quick_gelu(int dtype, int64_t n, const void* c, const void* c_t, void* a, void* a_t, void* stream) {
+  CHECK_ARG(n > 0 && c && (c_t ? a_t != nullptr : a != nullptr), "null pointer / empty problem");
+  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
+  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
+  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
+  const int64_t ch = n / ce;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MDD_DTYPE_F32) {
+    if (c_t) k_quick_gelu_fwd<Dual, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, (const float*)c_t, (float*)a, (float*)a_t, ch);
+    else k_quick_gelu_fwd<float, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, nullptr, (float*)a, nullptr, ch);
+  } else {
+    if (c_t) k_quick_gelu_fwd<Dual, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, (const bf16*)c_t, (bf16*)a, (bf16*)a_t, ch);
+    else k_quick_gelu_fwd<float, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, nullptr, (bf16*)a, nullptr, ch);
+  }
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+int mdd_op_quick_gelu_bwd(int dtype, int64_t n, const void* c, const void* c_t, const void* abar, const void* abar_t,
+                          void* cbar, void* cbar_t, void* stream) {
+  CHECK_ARG(n > 0 && c && abar, "null pointer / empty problem");
+  const bool T = c_t != nullptr;
+  CHECK_ARG(T == (abar_t != nullptr) && (T ? cbar_t != nullptr : cbar != nullptr), "tangent operands come together");
+  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
+  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
+  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
+  const int64_t ch = n / ce;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MDD_DTYPE_F32) {
+    if (T) k_quick_gelu_bwd<Dual, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, (const float*)c_t, (const float*)abar, (const float*)abar_t, (float*)cbar, (float*)cbar_t, ch);
+    else k_quick_gelu_bwd<float, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, nullptr, (const float*)abar, nullptr, (float*)cbar, nullptr, ch);
+  } else {
+    if (T) k_quick_gelu_bwd<Dual, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, (const bf16*)c_t, (const bf16*)abar, (const bf16*)abar_t, (bf16*)cbar, (bf16*)cbar_t, ch);
+    else k_quick_gelu_bwd<float, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, nullptr, (const bf16*)abar, nullptr, (bf16*)cbar, nullptr, ch);
   }
   HIP_CHECK_RET(hipGetLastError());
   return 0;

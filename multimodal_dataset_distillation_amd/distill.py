@@ -89,7 +89,7 @@ def build_parser():
     p.add_argument("--k_test", type=int, default=128)
     p.add_argument("--load_npy", type=bool, default=False)
     p.add_argument("--image_encoder", type=str, default="nfnet",
-                   help="nfnet | vit | nf_resnet50 | nf_regnet (the reference's names) or an engine variant "
+                   help="nfnet | vit | nf_resnet50 | nf_regnet | clip (the reference's names) or an engine variant "
                         "(networks.VARIANTS)")
     p.add_argument("--text_encoder", type=str, default="bert", choices=["bert", "clip"])
     p.add_argument("--margin", default=0.2, type=float)
@@ -354,6 +354,10 @@ def main(args):
                losses=torch.zeros(3 + args.syn_steps, device=device))
 
     # ---- expert buffers (distill.py:255-283)
+    # the reference's `clip` expert files hold the whole CLIP parameter list per snapshot (text tower included, fp16): the
+    # student's visual tower is sliced out of it by its shape sequence (expert_buffer.flatten_trajectories)
+    img_table = eng.param_table("img")
+    img_shapes = [s for _, s, _ in img_table] if img_table[0][0].startswith("model.visual.") else None
     if args.synthetic_experts:
         E, T = args.synthetic_experts
         buf = synthetic_buffer(eng, E, T, seed=args.seed + (0 if mode_b else rank), device=device)
@@ -366,7 +370,7 @@ def main(args):
         img_files, txt_files = shuffle_files(img_files, txt_files)
         files = (img_files, txt_files)
         print("loading file {}".format(img_files[0]))
-        buf = ExpertBuffer.from_files(img_files[0], txt_files[0], eng.P_img, eng.P_txt, device)
+        buf = ExpertBuffer.from_files(img_files[0], txt_files[0], eng.P_img, eng.P_txt, device, img_shapes=img_shapes)
     file_idx = expert_idx = 0
 
     student = img_net = txt_net = None
@@ -401,7 +405,7 @@ def main(args):
                 if args.max_files != 1:
                     print("loading file {}".format(files[0][file_idx]))
                     buf = ExpertBuffer.from_files(files[0][file_idx], files[1][file_idx], eng.P_img,
-                                                  eng.P_txt, device)
+                                                  eng.P_txt, device, img_shapes=img_shapes)
         start_epoch = np.random.randint(0, args.max_start_epoch)
         th0i, th0t, tgi, tgt = buf.pick(e_idx, start_epoch, args.expert_epochs)
         perms = torch.stack([torch.randperm(args.num_queries)[:batch] for _ in range(args.syn_steps)]).to(device)

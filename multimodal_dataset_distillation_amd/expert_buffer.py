@@ -33,9 +33,32 @@ def shuffle_files(img_files, txt_files, rng=np.random):
     return [img_files[i] for i in order], [txt_files[i] for i in order]
 
 
+def _find_run(got, want):
+    """Start of the one contiguous run of `got` (a snapshot's tensor shapes) that equals `want`."""
+    n = len(want)
+    hits = [i for i in range(len(got) - n + 1) if got[i:i + n] == want]
+    if len(hits) != 1:
+        raise ValueError("expert buffer snapshots hold %d tensors, the student %d: its shape sequence occurs %d times "
+                         "in them (exactly one contiguous run is needed to slice the student's parameters out)"
+                         % (len(got), n, len(hits)))
+    return hits[0]
+
+
 def flatten_trajectories(trajs, expect_numel=None, expect_shapes=None):
     """list[expert][epoch][tensor] -> fp32 tensor [E, T, P] (reference distill.py:469-476 does the
-    same `cat(p.reshape(-1))` per use)."""
+    same `cat(p.reshape(-1))` per use).  A snapshot with MORE tensors than `expect_shapes` is a whole-model parameter
+    list that holds the student's as one contiguous run (the reference's `clip` image encoder saves the whole CLIP
+    object, text tower included, usually in fp16; the student is its visual tower): the run is located by its shape
+    sequence and sliced out of every snapshot."""
+    if expect_shapes is not None and len(trajs[0][0]) > len(expect_shapes):
+        want = [tuple(s) for s in expect_shapes]
+        n_all = len(trajs[0][0])
+        i0 = _find_run([tuple(p.shape) for p in trajs[0][0]], want)
+        for traj in trajs:
+            for snap in traj:
+                if len(snap) != n_all or [tuple(p.shape) for p in snap[i0:i0 + len(want)]] != want:
+                    raise ValueError("expert buffer snapshots differ in their parameter lists")
+        trajs = [[snap[i0:i0 + len(want)] for snap in traj] for traj in trajs]
     E, T = len(trajs), len(trajs[0])
     P = sum(int(p.numel()) for p in trajs[0][0])
     if expect_numel is not None and P != expect_numel:
@@ -77,8 +100,10 @@ class ExpertBuffer:
         self.num_experts, self.num_snapshots = self.img.shape[:2]
 
     @classmethod
-    def from_files(cls, img_path, txt_path, P_img, P_txt, device="cuda"):
-        return cls(load_expert_file(img_path, expect_numel=P_img),
+    def from_files(cls, img_path, txt_path, P_img, P_txt, device="cuda", img_shapes=None):
+        """img_shapes (the student's image-parameter shapes in flatten order): also accept whole-model snapshots that
+        hold them as one contiguous run (flatten_trajectories)."""
+        return cls(load_expert_file(img_path, expect_numel=P_img, expect_shapes=img_shapes),
                    load_expert_file(txt_path, expect_numel=P_txt), device)
 
     def pick(self, expert_idx, start_epoch, expert_epochs):

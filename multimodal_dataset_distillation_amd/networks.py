@@ -23,8 +23,16 @@ from . import functional as Fn
 # reference networks.py:660-676 names -> engine topologies.  'vit' there is timm.create_model('vit_tiny_patch16_224')
 # WITHOUT num_classes=0 (:668): the model keeps timm's 1000-way head (5,717,416 parameters, 1000-d features into the
 # projection, networks.py:819) = 'vit_tiny16_cls' here, so reference-format 'vit' expert buffers flatten to P_img.
-# 'vit_tiny16' (headless, 192-d class token) and 'vit_b16' (BASELINE configs[4]'s ViT-B/16; the reference's 'clip' is
-# ViT-B/32 through the clip package) are build-defined.  'nf_resnet50' is timm.create_model('nf_resnet50', pretrained=True)
+# 'vit_tiny16' (headless, 192-d class token) and 'vit_b16' (BASELINE configs[4]'s ViT-B/16) are build-defined.
+# 'clip' is OpenAI's ViT-B/32 image tower used through encode_image (networks.py:659-662) = 'clip_vit_b32': QuickGELU,
+# ln_pre, bias-free patch-32 convolution, bias-free projection to 512 features, the clip package's parameter names under
+# model.visual.* (87,849,216 parameters); 'clip_vit_micro' / 'clip_vit_nano' are its build-defined miniatures.  Only the
+# visual tower is the student's theta: the reference's ImageEncoder.model.parameters() also lists CLIP's text tower, which
+# gets no gradient in either stage (theta* = theta0 there: 0 in the matching loss's numerator and denominator), and
+# reference-format expert files are read by slicing the visual run out (expert_buffer.flatten_trajectories).  The text
+# projection maps to the encoder's 512 features here; the reference's CLIPModel_full gives every encoder but nfnet
+# image_embedding = 1000 (networks.py:819), with which x @ y.T cannot run for 512-d image features: its clip path fails
+# as checked in, this one follows the encoder's width.  'nf_resnet50' is timm.create_model('nf_resnet50', pretrained=True)
 # (networks.py:669-670), also with its 1000-way head: 1000-d features; 'nf_resnet_tiny' is its build-defined miniature.
 # 'nf_regnet' is timm.create_model('nf_regnet_b1', pretrained=True) (networks.py:671-672), head kept as well: 1000-d
 # features; 'nf_regnet_tiny' is its build-defined miniature.
@@ -32,7 +40,9 @@ VARIANTS = {"nfnet": "nfnet_l0", "nfnet_l0": "nfnet_l0", "nfnet_l1": "nfnet_l1",
             "nfnet_tiny": "nfnet_tiny", "vit": "vit_tiny16_cls", "vit_tiny16_cls": "vit_tiny16_cls",
             "vit_tiny16": "vit_tiny16", "vit_b16": "vit_b16", "vit_micro": "vit_micro", "vit_micro_cls": "vit_micro_cls",
             "nf_resnet50": "nf_resnet50", "nf_resnet_tiny": "nf_resnet_tiny",
-            "nf_regnet": "nf_regnet_b1", "nf_regnet_b1": "nf_regnet_b1", "nf_regnet_tiny": "nf_regnet_tiny"}
+            "nf_regnet": "nf_regnet_b1", "nf_regnet_b1": "nf_regnet_b1", "nf_regnet_tiny": "nf_regnet_tiny",
+            "clip": "clip_vit_b32", "clip_vit_b32": "clip_vit_b32", "clip_vit_micro": "clip_vit_micro",
+            "clip_vit_nano": "clip_vit_nano"}
 
 _ENGINES = {}
 
@@ -79,6 +89,40 @@ def init_image_params(table, generator=None, trained_like=False):
     gains/biases the way oracle/nfnet_ref.randomize_like_trained does (synthetic expert snapshots; default
     init zeroes most of the theta-gradient)."""
     out = []
+    if any(name == "model.visual.class_embedding" for name, _, _ in table):
+        # OpenAI clip VisionTransformer as torch constructs it: width^-0.5 * randn class / positional embedding and proj,
+        # xavier_uniform in_proj_weight with zero in_proj_bias and out_proj.bias (nn.MultiheadAttention), nn.Linear /
+        # nn.Conv2d defaults elsewhere (kaiming_uniform(a = sqrt 5): U(+-1/sqrt(fan_in)) weights and biases), unit
+        # LayerNorm gains with zero biases; trained_like perturbs gains / biases / the class token, as for timm's ViT
+        width = int(next(shape for name, shape, _ in table if name.endswith("class_embedding"))[0])
+
+        def uniform(shape, bound):
+            return (torch.rand(shape, generator=generator) * 2 - 1) * bound
+        for name, shape, _ in table:
+            leaf = name.rsplit(".", 1)[-1]
+            if leaf in ("class_embedding", "positional_embedding", "proj"):
+                t = width ** -0.5 * torch.randn(shape, generator=generator)
+                if leaf == "class_embedding" and trained_like:
+                    t = t + 0.02 * torch.randn(shape, generator=generator)
+            elif ".ln_" in name or "ln_pre" in name or "ln_post" in name:
+                if leaf == "weight":
+                    t = 1.0 + (0.1 * torch.randn(shape, generator=generator) if trained_like else 0.0) * torch.ones(shape)
+                else:
+                    t = 0.02 * torch.randn(shape, generator=generator) if trained_like else torch.zeros(shape)
+            elif leaf == "in_proj_weight":
+                t = uniform(shape, math.sqrt(6.0 / (shape[0] + shape[1])))
+            elif leaf == "in_proj_bias" or name.endswith("out_proj.bias"):
+                t = 0.02 * torch.randn(shape, generator=generator) if trained_like else torch.zeros(shape)
+            elif leaf == "weight":
+                fan_in = 1
+                for d in shape[1:]:
+                    fan_in *= int(d)
+                t = uniform(shape, 1.0 / math.sqrt(fan_in))
+            else:   # c_fc / c_proj biases: U(+-1/sqrt(fan_in)) of their own linear
+                fan_in = {"c_fc": width, "c_proj": 4 * width}[name.split(".")[-2]]
+                t = uniform(shape, 1.0 / math.sqrt(fan_in))
+            out.append(t)
+        return out
     if any(name == "model.cls_token" for name, _, _ in table):
         # timm VisionTransformer init: trunc_normal(0.02) linear weights and position embedding, zero biases, unit
         # LayerNorm gains, class token N(0, 1e-6); trained_like perturbs gains / biases / class token

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B timing of library builds on the benched workload (C2 iteration, no SGD / self-check):
-    python tools/ab_bench.py [--dtype bf16] [--steps 6] [--workload c2|c1|c5|res|reg] libA.so libB.so ...
+    python tools/ab_bench.py [--dtype bf16] [--steps 6] [--workload c2|c1|c5|res|reg|clip] libA.so libB.so ...
 Each library runs in its own child process (the C-ABI library is loaded once per process); prints
 ms/iteration and the per-class HIP-event times of one instrumented iteration."""
 import argparse
@@ -28,7 +28,9 @@ def one(lib_path, dtype, steps, workload, own_stream=False):
     # res / reg: the other two NormFreeNet walkers at c2's pairs, steps, image size and d_txt
     variant, n, K, size, d_txt = {"c2": ("nfnet_l0", 100, 8, 224, 768), "c1": ("nfnet_l0", 10, 2, 224, 768),
                                  "c5": ("vit_b16", 100, 8, 224, 512), "res": ("nf_resnet50", 100, 8, 224, 768),
-                                 "reg": ("nf_regnet_b1", 100, 8, 224, 768)}[workload]
+                                 "reg": ("nf_regnet_b1", 100, 8, 224, 768),
+                                 # clip: the reference's --image_encoder clip (ViT-B/32 tower) with CLIP's 512-d text embeddings
+                                 "clip": ("clip_vit_b32", 100, 8, 224, 512)}[workload]
     dev = torch.device("cuda", 0)
     eng = UnrollEngine(variant, batch=n, num_queries=n, image_size=size, d_txt=d_txt, syn_steps=K, dtype=dtype, device=dev)
     lib = _lib.load()
@@ -74,7 +76,7 @@ def main():
     ap.add_argument("--one", default=None)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--steps", type=int, default=6)
-    ap.add_argument("--workload", default="c2", choices=["c2", "c1", "c5", "res", "reg"])
+    ap.add_argument("--workload", default="c2", choices=["c2", "c1", "c5", "res", "reg", "clip"])
     ap.add_argument("--stream", nargs="?", const="normal", default=None, choices=["normal", "high"],
                     help="run on a non-default HIP stream; 'high' = a high-priority stream")
     ap.add_argument("libs", nargs="*")
