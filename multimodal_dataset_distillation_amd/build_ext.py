@@ -1,4 +1,5 @@
-"""Builds csrc/*.hip (the engine is csrc/engine.hip) into the in-tree C-ABI shared library libmdd_hip.so for gfx950.
+"""Builds csrc/*.hip into the in-tree C-ABI shared library libmdd_hip.so for gfx950: the engine (csrc/engine.hip), the
+stateless op-level entry points (csrc/ops_abi.hip) and the kernel translation units; csrc/host.h is their shared host glue.
 
 `python -m multimodal_dataset_distillation_amd.build_ext` (or `__graft_entry__.build()`).
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels with gpurun snapshots.
@@ -15,10 +16,10 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmdd_hip.so")
 SOURCES = ["flat_ops.hip", "ws.hip", "elementwise.hip", "linear.hip", "head.hip", "conv_gemm.hip",
            "conv_gemm_relu.hip", "conv_gemm_qgelu.hip", "conv_wgrad.hip", "retrieval.hip", "collective.hip", "vit.hip", "attn.hip",
-           "nfres.hip", "nfreg.hip", "conv_g8.hip", "engine.hip"]
+           "nfres.hip", "nfreg.hip", "conv_g8.hip", "ops_abi.hip", "engine.hip"]
 # sources that include another source file: rebuilt when it changes
 INCLUDES = {"conv_gemm_relu.hip": ["conv_gemm.hip"], "conv_gemm_qgelu.hip": ["conv_gemm.hip"]}
-HEADERS = ["common.h", "kernels.h", "philox.h", "conv_gemm_epilogue.inc", "conv_gemm_epilogue_se.inc", os.path.join("..", "..", "include", "mdd_hip.h")]
+HEADERS = ["common.h", "host.h", "kernels.h", "philox.h", "conv_gemm_epilogue.inc", "conv_gemm_epilogue_se.inc", os.path.join("..", "..", "include", "mdd_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result",
          "-I", os.path.join(HERE, "..", "include")]
 

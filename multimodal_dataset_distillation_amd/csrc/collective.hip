@@ -20,9 +20,6 @@
 #include "kernels.h"
 #include "mdd_hip.h"
 
-#define CHECK_ARG(cond, msg) \
-  do { if (!(cond)) return mdd_set_error_msg(2, "mdd: invalid argument: " msg); } while (0)
-
 namespace {
 
 struct Rccl {

@@ -1,9 +1,8 @@
-// Launcher declarations shared by the engine (engine.cpp) and the kernel translation units.
+// Launcher declarations shared by the engine (engine.hip), the op-level entry points (ops_abi.hip) and the kernel
+// translation units.
 #pragma once
 #include "common.h"
-
-int mdd_set_error(hipError_t e, const char* what);
-int mdd_set_error_msg(int code, const char* msg);
+#include "host.h"
 
 // ---------------------------------------------------------------- flat_ops.hip (fp32 theta)
 void launch_axpy_out(float* y, const float* x, const float* g, const float* lr, float sign,
@@ -35,6 +34,12 @@ struct WsDesc {
   int tile_start;               // prefix sum of groups * ceil(cout_g / ws_tile_rows()) (ws_forward blocks)
 };
 int ws_tile_rows();
+// Descriptor of one conv [cout][cin / groups][k][k] whose parameters sit at off_w / off_b / off_g of theta and whose packed
+// weights sit at off_p of both packed buffers (cin_pad input channels; esize bytes per packed element).  row and tile are
+// the running prefix sums over the convs so far: read for row_start / tile_start, then advanced.  false: cin_pad / groups
+// or cout / groups is no multiple of the 16-byte chunk (d is filled all the same).
+bool ws_desc_fill(WsDesc& d, int cout, int cin, int k, int groups, int cin_pad, int64_t off_w, int64_t off_b, int64_t off_g,
+                  int64_t off_p, float gamma, float eps, int64_t& row, int64_t& tile, int esize);
 // theta_t == nullptr: primal (writes wf, wt).  theta_t != nullptr: tangent pass (writes wf_t,
 // wt_t, and re-derives the primal wf, wt from theta when those pointers are non-null).
 template <class AT>
@@ -324,6 +329,12 @@ int64_t loss_work_floats(int n, int d);
 // 64 KiB a workgroup may ask for, and an n whose n * n does not fit an int
 int contrastive_max_d();
 int64_t contrastive_lds_bytes(int n);
+#define CHECK_CONTRASTIVE(n, d)                                                                                        \
+  do {                                                                                                                 \
+    CHECK_ARG((int64_t)(n) * (n) <= 2147483647ll, "contrastive head: n * n overflows int");                            \
+    CHECK_ARG(contrastive_lds_bytes(n) <= 65536, "contrastive head: n needs more than the 64 KiB of LDS a workgroup may ask for (n <= 4092)"); \
+    CHECK_ARG((d) <= contrastive_max_d(), "contrastive head: d > 4096 (16 x 256 feature registers per row)");          \
+  } while (0)
 LossWork loss_work_carve(float* base, int n, int d);
 void launch_contrastive(const LossWork& w, float* loss, float* xbar, float* ybar, float* sbar,
                         float* xbar_t, float* ybar_t, float* sbar_t, const float* x,
@@ -349,6 +360,9 @@ template <class AT> void launch_cls_put(AT* a, const float* fa, AT* b, const flo
 template <class AT> void launch_act_to_f32(float* o, const AT* a, int64_t n, hipStream_t st);
 template <class AT> void launch_f32_to_act(AT* o, const float* a, int64_t n, hipStream_t st);
 struct LinPackDesc { int64_t off_w, off_p; int out, in, tile_start, pad_; };
+// Descriptor of one linear W [out][in] at off_w of theta, packed at off_p of both packed buffers.  tiles is the running
+// prefix sum of the blocks k_lin_pack_all gives the linears so far: read for tile_start, then advanced.
+LinPackDesc lin_pack_desc(int out, int in, int64_t off_w, int64_t off_p, int64_t& tiles);
 template <class AT> void launch_lin_pack_all(const LinPackDesc* descs, int nd, int total_tiles, const float* th, const float* th_t,
                                              AT* wf, AT* wt, AT* wf_t, AT* wt_t, hipStream_t st);
 

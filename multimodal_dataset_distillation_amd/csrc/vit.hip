@@ -5,16 +5,14 @@
 // the NFNet elementwise kernels do.  Tangent calls read the primal operands and write ONLY the tangent outputs.
 // Reference: the reference reaches its transformers through timm / clip (networks.py:661,668); what is implemented
 // is timm 0.6.7's VisionTransformer block as restated in oracle/vit_ref.py.
-// Status: op-level entry points (include/mdd_hip.h `mdd_op_*`), parity-tested against torch; the engine topology
-// that walks them is the next step.
+// The op-level entry points at the end (include/mdd_hip.h `mdd_op_*`) are parity-tested against torch, and they are the
+// launchers the engine's vit_forward / vit_backward call.
 #include <algorithm>
 #include <type_traits>
 
 #include "kernels.h"
 #include "mdd_hip.h"
 
-#define CHECK_ARG(cond, msg) \
-  do { if (!(cond)) return mdd_set_error_msg(2, "mdd: invalid argument: " msg); } while (0)
 #ifndef MDD_LN_BWD_ROWS
 #define MDD_LN_BWD_ROWS 16   // rows per block of k_ln_bwd (four waves, one row per wave at a time): the parameter-gradient sums cost
                              // one fp32 atomic per column and block
@@ -790,44 +788,32 @@ inline int vgrid(int64_t items, int block = 256) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, 8192));
 }
 
-template <class AT>
-int ln_fwd(int rows, int dim, float eps, const void* x, const void* x_t, const float* g, const float* g_t,
-           const float* b, const float* b_t, void* y, void* y_t, hipStream_t st, const void* ra = nullptr,
-           const void* rb = nullptr, void* rs = nullptr) {
+// S = float ignores every tangent pointer (ldcS / stcS / ldp4 and the Dual-only branches of the kernels), so the primal
+// and the tangent call pass the same argument list
+template <class S, class AT>
+void ln_fwd(int rows, int dim, float eps, const void* x, const void* x_t, const float* g, const float* g_t,
+            const float* b, const float* b_t, void* y, void* y_t, hipStream_t st, const void* ra = nullptr,
+            const void* rb = nullptr, void* rs = nullptr) {
   const int cch = dim / Chunk<AT>::N, maxc = (cch + 63) / 64;
   const int grid = (rows + 3) / 4;
-#define LN_F(MC)                                                                                                \
-  do {                                                                                                          \
-    if (g_t) k_ln_fwd<Dual, AT, MC><<<grid, 256, 0, st>>>((const AT*)x, (const AT*)x_t, g, g_t, b, b_t, (AT*)y,  \
-                                                          (AT*)y_t, rows, dim, eps, (const AT*)ra, (const AT*)rb, \
-                                                          (AT*)rs);                                             \
-    else k_ln_fwd<float, AT, MC><<<grid, 256, 0, st>>>((const AT*)x, nullptr, g, nullptr, b, nullptr, (AT*)y,    \
-                                                       nullptr, rows, dim, eps, (const AT*)ra, (const AT*)rb,   \
-                                                       (AT*)rs);                                                \
-  } while (0)
+#define LN_F(MC)                                                                                                        \
+  k_ln_fwd<S, AT, MC><<<grid, 256, 0, st>>>((const AT*)x, (const AT*)x_t, g, g_t, b, b_t, (AT*)y, (AT*)y_t, rows, dim, eps, \
+                                            (const AT*)ra, (const AT*)rb, (AT*)rs)
   if (maxc == 1) LN_F(1); else if (maxc == 2) LN_F(2); else if (maxc == 3) LN_F(3); else LN_F(4);
 #undef LN_F
-  return 0;
 }
-template <class AT>
-int ln_bwd(int rows, int dim, float eps, const void* x, const void* x_t, const void* dy, const void* dy_t,
-           const float* g, const float* g_t, const void* res, const void* res_t, void* dx, void* dx_t, float* dg,
-           float* dg_t, float* db, float* db_t, hipStream_t st) {
+template <class S, class AT>
+void ln_bwd(int rows, int dim, float eps, const void* x, const void* x_t, const void* dy, const void* dy_t,
+            const float* g, const float* g_t, const void* res, const void* res_t, void* dx, void* dx_t, float* dg,
+            float* dg_t, float* db, float* db_t, hipStream_t st) {
   const int cch = dim / Chunk<AT>::N, maxc = (cch + 63) / 64;
   const int rpb = MDD_LN_BWD_ROWS, grid = (rows + rpb - 1) / rpb;
-#define LN_B(MC)                                                                                                 \
-  do {                                                                                                           \
-    if (x_t) k_ln_bwd<Dual, AT, MC><<<grid, 256, 0, st>>>((const AT*)x, (const AT*)x_t, (const AT*)dy,            \
-                                                          (const AT*)dy_t, g, g_t, (const AT*)res,               \
-                                                          (const AT*)res_t, (AT*)dx, (AT*)dx_t, dg, dg_t,        \
-                                                          db, db_t, rows, dim, eps, rpb);                        \
-    else k_ln_bwd<float, AT, MC><<<grid, 256, 0, st>>>((const AT*)x, nullptr, (const AT*)dy, nullptr, g, nullptr, \
-                                                       (const AT*)res, nullptr, (AT*)dx, nullptr, dg, nullptr,   \
-                                                       db, nullptr, rows, dim, eps, rpb);                        \
-  } while (0)
+#define LN_B(MC)                                                                                                        \
+  k_ln_bwd<S, AT, MC><<<grid, 256, 0, st>>>((const AT*)x, (const AT*)x_t, (const AT*)dy, (const AT*)dy_t, g, g_t,        \
+                                            (const AT*)res, (const AT*)res_t, (AT*)dx, (AT*)dx_t, dg, dg_t, db, db_t,   \
+                                            rows, dim, eps, rpb)
   if (maxc == 1) LN_B(1); else if (maxc == 2) LN_B(2); else LN_B(3);
 #undef LN_B
-  return 0;
 }
 // bf16 storage: the matrix-core kernel for the two operand-type patterns attention uses
 template <bool DUAL>
@@ -956,6 +942,11 @@ __global__ __launch_bounds__(256) void k_lin_pack_all(const LinPackDesc* __restr
     }
   }
 }
+LinPackDesc lin_pack_desc(int out, int in, int64_t off_w, int64_t off_p, int64_t& tiles) {
+  LinPackDesc d; d.off_w = off_w; d.off_p = off_p; d.out = out; d.in = in; d.tile_start = (int)tiles; d.pad_ = 0;
+  tiles += (int64_t)((in + 63) / 64) * ((out + 63) / 64);      // k_lin_pack_all: 64 x 64 tiles
+  return d;
+}
 template <class AT>
 void launch_lin_pack_all(const LinPackDesc* descs, int nd, int total_tiles, const float* th, const float* th_t,
                          AT* wf, AT* wt, AT* wf_t, AT* wt_t, hipStream_t st) {
@@ -981,6 +972,40 @@ VIT_INST(float)
 VIT_INST(bf16)
 #undef VIT_INST
 
+// the chunk activations: exact GELU, or CLIP's QuickGELU
+static int act_fwd(bool quick, int dtype, int64_t n, const void* c, const void* c_t, void* a, void* a_t, void* stream) {
+  CHECK_ARG(n > 0 && c && (c_t ? a_t != nullptr : a != nullptr), "null pointer / empty problem");
+  CHECK_STORAGE(dtype);
+  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
+  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
+  const int64_t ch = n / ce;
+  with_scalar_storage(c_t != nullptr, dtype, [&](auto* s, auto* at) {
+    using S = tag_t<decltype(s)>; using AT = tag_t<decltype(at)>;
+    auto* k = quick ? k_quick_gelu_fwd<S, AT> : k_gelu_fwd<S, AT>;
+    k<<<vgrid(ch), 256, 0, (hipStream_t)stream>>>((const AT*)c, (const AT*)c_t, (AT*)a, (AT*)a_t, ch);
+  });
+  POST_LAUNCH("act_fwd");
+  return 0;
+}
+static int act_bwd(bool quick, int dtype, int64_t n, const void* c, const void* c_t, const void* abar, const void* abar_t,
+                   void* cbar, void* cbar_t, void* stream) {
+  CHECK_ARG(n > 0 && c && abar, "null pointer / empty problem");
+  const bool T = c_t != nullptr;
+  CHECK_ARG(T == (abar_t != nullptr) && (T ? cbar_t != nullptr : cbar != nullptr), "tangent operands come together");
+  CHECK_STORAGE(dtype);
+  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
+  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
+  const int64_t ch = n / ce;
+  with_scalar_storage(T, dtype, [&](auto* s, auto* at) {
+    using S = tag_t<decltype(s)>; using AT = tag_t<decltype(at)>;
+    auto* k = quick ? k_quick_gelu_bwd<S, AT> : k_gelu_bwd<S, AT>;
+    k<<<vgrid(ch), 256, 0, (hipStream_t)stream>>>((const AT*)c, (const AT*)c_t, (const AT*)abar, (const AT*)abar_t, (AT*)cbar,
+                                                  (AT*)cbar_t, ch);
+  });
+  POST_LAUNCH("act_bwd");
+  return 0;
+}
+
 extern "C" {
 
 int mdd_op_layernorm(int dtype, int rows, int dim, float eps, const void* x, const void* x_t, const float* gamma,
@@ -989,12 +1014,14 @@ int mdd_op_layernorm(int dtype, int rows, int dim, float eps, const void* x, con
   CHECK_ARG((x_t != nullptr) == (gamma_t != nullptr) && (x_t != nullptr) == (beta_t != nullptr) &&
                 (x_t != nullptr) == (y_t != nullptr), "tangent operands come together");
   CHECK_ARG(x_t || y, "output is null");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
+  CHECK_STORAGE(dtype);
   const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
   CHECK_ARG(dim % ce == 0 && dim / ce <= 256, "dim must be a multiple of the 16-byte chunk and at most 256 chunks");
-  if (dtype == MDD_DTYPE_F32) ln_fwd<float>(rows, dim, eps, x, x_t, gamma, gamma_t, beta, beta_t, y, y_t, (hipStream_t)stream);
-  else ln_fwd<bf16>(rows, dim, eps, x, x_t, gamma, gamma_t, beta, beta_t, y, y_t, (hipStream_t)stream);
-  HIP_CHECK_RET(hipGetLastError());
+  with_scalar_storage(gamma_t != nullptr, dtype, [&](auto* s, auto* at) {
+    using S = tag_t<decltype(s)>; using AT = tag_t<decltype(at)>;
+    ln_fwd<S, AT>(rows, dim, eps, x, x_t, gamma, gamma_t, beta, beta_t, y, y_t, (hipStream_t)stream);
+  });
+  POST_LAUNCH("op_layernorm");
   return 0;
 }
 
@@ -1004,13 +1031,15 @@ int mdd_op_add_layernorm(int dtype, int rows, int dim, float eps, const void* a,
   CHECK_ARG(rows > 0 && dim > 0 && s && gamma && beta, "null pointer / empty problem");
   const bool T = gamma_t != nullptr;
   CHECK_ARG(T ? (a_t && b_t && s_t && beta_t && y_t) : (a && b && y), "primal call: a, b, s, y; tangent call: s (primal sum), a_t, b_t, s_t, y_t");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
+  CHECK_STORAGE(dtype);
   const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
   CHECK_ARG(dim % ce == 0 && dim / ce <= 256, "dim must be a multiple of the 16-byte chunk and at most 256 chunks");
   const void* ra = T ? a_t : a; const void* rb = T ? b_t : b; void* rs = T ? s_t : s;
-  if (dtype == MDD_DTYPE_F32) ln_fwd<float>(rows, dim, eps, s, s_t, gamma, gamma_t, beta, beta_t, y, y_t, (hipStream_t)stream, ra, rb, rs);
-  else ln_fwd<bf16>(rows, dim, eps, s, s_t, gamma, gamma_t, beta, beta_t, y, y_t, (hipStream_t)stream, ra, rb, rs);
-  HIP_CHECK_RET(hipGetLastError());
+  with_scalar_storage(T, dtype, [&](auto* sc, auto* at) {
+    using S = tag_t<decltype(sc)>; using AT = tag_t<decltype(at)>;
+    ln_fwd<S, AT>(rows, dim, eps, s, s_t, gamma, gamma_t, beta, beta_t, y, y_t, (hipStream_t)stream, ra, rb, rs);
+  });
+  POST_LAUNCH("op_add_layernorm");
   return 0;
 }
 
@@ -1024,108 +1053,45 @@ int mdd_op_layernorm_bwd(int dtype, int rows, int dim, float eps, const void* x,
                 T == (dgamma_t != nullptr) && T == (dbeta_t != nullptr), "tangent operands come together");
   CHECK_ARG(!res || !T || res_t, "the residual gradient needs its tangent in a tangent call");
   CHECK_ARG(T || (dx && dgamma && dbeta), "output is null");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
+  CHECK_STORAGE(dtype);
   const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
   CHECK_ARG(dim % ce == 0 && dim / ce <= 192, "dim must be a multiple of the 16-byte chunk and at most 192 chunks");
-  if (dtype == MDD_DTYPE_F32) ln_bwd<float>(rows, dim, eps, x, x_t, dy, dy_t, gamma, gamma_t, res, res_t, dx, dx_t, dgamma, dgamma_t, dbeta, dbeta_t, (hipStream_t)stream);
-  else ln_bwd<bf16>(rows, dim, eps, x, x_t, dy, dy_t, gamma, gamma_t, res, res_t, dx, dx_t, dgamma, dgamma_t, dbeta, dbeta_t, (hipStream_t)stream);
-  HIP_CHECK_RET(hipGetLastError());
+  with_scalar_storage(T, dtype, [&](auto* s, auto* at) {
+    using S = tag_t<decltype(s)>; using AT = tag_t<decltype(at)>;
+    ln_bwd<S, AT>(rows, dim, eps, x, x_t, dy, dy_t, gamma, gamma_t, res, res_t, dx, dx_t, dgamma, dgamma_t, dbeta, dbeta_t,
+                  (hipStream_t)stream);
+  });
+  POST_LAUNCH("op_layernorm_bwd");
   return 0;
 }
 
 int mdd_op_gelu(int dtype, int64_t n, const void* c, const void* c_t, void* a, void* a_t, void* stream) {
-  CHECK_ARG(n > 0 && c && (c_t ? a_t != nullptr : a != nullptr), "null pointer / empty problem");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
-  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
-  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
-  const int64_t ch = n / ce;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDD_DTYPE_F32) {
-    if (c_t) k_gelu_fwd<Dual, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, (const float*)c_t, (float*)a, (float*)a_t, ch);
-    else k_gelu_fwd<float, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, nullptr, (float*)a, nullptr, ch);
-  } else {
-    if (c_t) k_gelu_fwd<Dual, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, (const bf16*)c_t, (bf16*)a, (bf16*)a_t, ch);
-    else k_gelu_fwd<float, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, nullptr, (bf16*)a, nullptr, ch);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return act_fwd(false, dtype, n, c, c_t, a, a_t, stream);
 }
-
 int mdd_op_gelu_bwd(int dtype, int64_t n, const void* c, const void* c_t, const void* abar, const void* abar_t,
                     void* cbar, void* cbar_t, void* stream) {
-  CHECK_ARG(n > 0 && c && abar, "null pointer / empty problem");
-  const bool T = c_t != nullptr;
-  CHECK_ARG(T == (abar_t != nullptr) && (T ? cbar_t != nullptr : cbar != nullptr), "tangent operands come together");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
-  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
-  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
-  const int64_t ch = n / ce;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDD_DTYPE_F32) {
-    if (T) k_gelu_bwd<Dual, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, (const float*)c_t, (const float*)abar, (const float*)abar_t, (float*)cbar, (float*)cbar_t, ch);
-    else k_gelu_bwd<float, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, nullptr, (const float*)abar, nullptr, (float*)cbar, nullptr, ch);
-  } else {
-    if (T) k_gelu_bwd<Dual, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, (const bf16*)c_t, (const bf16*)abar, (const bf16*)abar_t, (bf16*)cbar, (bf16*)cbar_t, ch);
-    else k_gelu_bwd<float, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, nullptr, (const bf16*)abar, nullptr, (bf16*)cbar, nullptr, ch);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return act_bwd(false, dtype, n, c, c_t, abar, abar_t, cbar, cbar_t, stream);
 }
-
 int mdd_op_quick_gelu(int dtype, int64_t n, const void* c, const void* c_t, void* a, void* a_t, void* stream) {
-  CHECK_ARG(n > 0 && c && (c_t ? a_t != nullptr : a != nullptr), "null pointer / empty problem");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
-  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
-  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
-  const int64_t ch = n / ce;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDD_DTYPE_F32) {
-    if (c_t) k_quick_gelu_fwd<Dual, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, (const float*)c_t, (float*)a, (float*)a_t, ch);
-    else k_quick_gelu_fwd<float, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, nullptr, (float*)a, nullptr, ch);
-  } else {
-    if (c_t) k_quick_gelu_fwd<Dual, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, (const bf16*)c_t, (bf16*)a, (bf16*)a_t, ch);
-    else k_quick_gelu_fwd<float, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, nullptr, (bf16*)a, nullptr, ch);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return act_fwd(true, dtype, n, c, c_t, a, a_t, stream);
 }
-
 int mdd_op_quick_gelu_bwd(int dtype, int64_t n, const void* c, const void* c_t, const void* abar, const void* abar_t,
                           void* cbar, void* cbar_t, void* stream) {
-  CHECK_ARG(n > 0 && c && abar, "null pointer / empty problem");
-  const bool T = c_t != nullptr;
-  CHECK_ARG(T == (abar_t != nullptr) && (T ? cbar_t != nullptr : cbar != nullptr), "tangent operands come together");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
-  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
-  CHECK_ARG(n % ce == 0, "element count must be a multiple of the 16-byte chunk");
-  const int64_t ch = n / ce;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDD_DTYPE_F32) {
-    if (T) k_quick_gelu_bwd<Dual, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, (const float*)c_t, (const float*)abar, (const float*)abar_t, (float*)cbar, (float*)cbar_t, ch);
-    else k_quick_gelu_bwd<float, float><<<vgrid(ch), 256, 0, st>>>((const float*)c, nullptr, (const float*)abar, nullptr, (float*)cbar, nullptr, ch);
-  } else {
-    if (T) k_quick_gelu_bwd<Dual, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, (const bf16*)c_t, (const bf16*)abar, (const bf16*)abar_t, (bf16*)cbar, (bf16*)cbar_t, ch);
-    else k_quick_gelu_bwd<float, bf16><<<vgrid(ch), 256, 0, st>>>((const bf16*)c, nullptr, (const bf16*)abar, nullptr, (bf16*)cbar, nullptr, ch);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return act_bwd(true, dtype, n, c, c_t, abar, abar_t, cbar, cbar_t, stream);
 }
 
 int mdd_op_softmax(int dtype, int64_t rows, int cols, int ld, float scale, const void* s, const void* s_t, void* p,
                    void* p_t, void* stream) {
   CHECK_ARG(rows > 0 && cols > 0 && cols <= 64 * SM_MAXE && ld >= cols && s, "rows / cols (<= 512) / ld");
   CHECK_ARG(s_t ? p_t != nullptr : p != nullptr, "output is null");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
+  CHECK_STORAGE(dtype);
   const unsigned grid = (unsigned)((rows + 3) / 4);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDD_DTYPE_F32) {
-    if (s_t) k_softmax_fwd<Dual, float><<<grid, 256, 0, st>>>((const float*)s, (const float*)s_t, (float*)p, (float*)p_t, rows, cols, ld, scale);
-    else k_softmax_fwd<float, float><<<grid, 256, 0, st>>>((const float*)s, nullptr, (float*)p, nullptr, rows, cols, ld, scale);
-  } else {
-    if (s_t) k_softmax_fwd<Dual, bf16><<<grid, 256, 0, st>>>((const bf16*)s, (const bf16*)s_t, (bf16*)p, (bf16*)p_t, rows, cols, ld, scale);
-    else k_softmax_fwd<float, bf16><<<grid, 256, 0, st>>>((const bf16*)s, nullptr, (bf16*)p, nullptr, rows, cols, ld, scale);
-  }
-  HIP_CHECK_RET(hipGetLastError());
+  with_scalar_storage(s_t != nullptr, dtype, [&](auto* sc, auto* at) {
+    using S = tag_t<decltype(sc)>; using AT = tag_t<decltype(at)>;
+    k_softmax_fwd<S, AT><<<grid, 256, 0, (hipStream_t)stream>>>((const AT*)s, (const AT*)s_t, (AT*)p, (AT*)p_t, rows, cols, ld,
+                                                                scale);
+  });
+  POST_LAUNCH("op_softmax");
   return 0;
 }
 
@@ -1134,17 +1100,14 @@ int mdd_op_softmax_bwd(int dtype, int64_t rows, int cols, int ld, float scale, c
   CHECK_ARG(rows > 0 && cols > 0 && cols <= 64 * SM_MAXE && ld >= cols && p && dp, "rows / cols (<= 512) / ld");
   const bool T = p_t != nullptr;
   CHECK_ARG(T == (dp_t != nullptr) && (T ? ds_t != nullptr : ds != nullptr), "tangent operands come together");
-  CHECK_ARG(dtype == MDD_DTYPE_F32 || dtype == MDD_DTYPE_BF16, "dtype");
+  CHECK_STORAGE(dtype);
   const unsigned grid = (unsigned)((rows + 3) / 4);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDD_DTYPE_F32) {
-    if (T) k_softmax_bwd<Dual, float><<<grid, 256, 0, st>>>((const float*)p, (const float*)p_t, (const float*)dp, (const float*)dp_t, (float*)ds, (float*)ds_t, rows, cols, ld, scale);
-    else k_softmax_bwd<float, float><<<grid, 256, 0, st>>>((const float*)p, nullptr, (const float*)dp, nullptr, (float*)ds, nullptr, rows, cols, ld, scale);
-  } else {
-    if (T) k_softmax_bwd<Dual, bf16><<<grid, 256, 0, st>>>((const bf16*)p, (const bf16*)p_t, (const bf16*)dp, (const bf16*)dp_t, (bf16*)ds, (bf16*)ds_t, rows, cols, ld, scale);
-    else k_softmax_bwd<float, bf16><<<grid, 256, 0, st>>>((const bf16*)p, nullptr, (const bf16*)dp, nullptr, (bf16*)ds, nullptr, rows, cols, ld, scale);
-  }
-  HIP_CHECK_RET(hipGetLastError());
+  with_scalar_storage(T, dtype, [&](auto* sc, auto* at) {
+    using S = tag_t<decltype(sc)>; using AT = tag_t<decltype(at)>;
+    k_softmax_bwd<S, AT><<<grid, 256, 0, (hipStream_t)stream>>>((const AT*)p, (const AT*)p_t, (const AT*)dp, (const AT*)dp_t,
+                                                                (AT*)ds, (AT*)ds_t, rows, cols, ld, scale);
+  });
+  POST_LAUNCH("op_softmax_bwd");
   return 0;
 }
 
@@ -1179,7 +1142,7 @@ int mdd_op_bgemm(int dtype, int a_is_f32, int c_is_f32, const mdd_bgemm_desc* d,
       else bgemm_types<float, bf16>(p, a_is_f32, c_is_f32, grid, st);
     }
   }
-  HIP_CHECK_RET(hipGetLastError());
+  POST_LAUNCH("op_bgemm");
   return 0;
 }
 

@@ -223,6 +223,19 @@ __global__ void k_ws_backward(const WsDesc* __restrict__ descs, int nconv, int t
 
 int ws_tile_rows() { return TR; }
 
+bool ws_desc_fill(WsDesc& d, int cout, int cin, int k, int groups, int cin_pad, int64_t off_w, int64_t off_b, int64_t off_g,
+                  int64_t off_p, float gamma, float eps, int64_t& row, int64_t& tile, int esize) {
+  d.off_w = off_w; d.off_b = off_b; d.off_g = off_g;
+  d.off_wf = off_p; d.off_wt = off_p;
+  d.cout = cout; d.cin_g = cin / groups; d.ksq = k * k; d.groups = groups;
+  d.cin_pad_g = cin_pad / groups; d.cout_g = cout / groups;
+  d.scale = gamma / std::sqrt((float)(d.cin_g * d.ksq)); d.eps = eps;
+  d.row_start = (int)row; row += cout;
+  d.tile_start = (int)tile; tile += d.groups * ((d.cout_g + TR - 1) / TR);
+  const int ce = 16 / esize;
+  return d.cin_pad_g % ce == 0 && d.cout_g % ce == 0;
+}
+
 template <class AT>
 void launch_ws_forward(const WsDesc* descs, int nconv, int total_rows, int total_tiles, const float* theta,
                        const float* theta_t, AT* wf, AT* wt, AT* wf_t, AT* wt_t, hipStream_t st) {

@@ -274,7 +274,7 @@ LP_LAUNCHES = {
 
 
 def lp_descs(shapes):
-    """(off_w, off_p, out, in, tile_start) per linear and the tile total, as Eng::create / mdd_op_lin_pack build them"""
+    """(off_w, off_p, out, in, tile_start) per linear and the tile total, as lin_pack_desc (csrc/vit.hip) builds them"""
     descs, off_w, off_p, tiles = [], 0, 0, 0
     for out, inn in shapes:
         descs.append((off_w, off_p, out, inn, tiles))
