@@ -72,7 +72,9 @@ const char* mdd_last_error(void);
  * mdd_op_resid, mdd_flat_dot / _scale_out / _sub_inplace / _lambda_init / _match_finalize / _d2f / _accum_f2d; 13 = +
  * in-engine dropout masks (mdd_iter_args.drop_p / drop_iteration / drop_seed, mdd_txt_forward_rng, mdd_op_dropout_mask,
  * mdd_sizeof_iter_args); still 13 (new symbols only, no struct changed): + mdd_op_quick_gelu / mdd_op_quick_gelu_bwd and the
- * CLIP ViT variants.  A binding built against another version must refuse to load. */
+ * CLIP ViT variants; still 13 (new symbols only, no struct changed): + the frozen CLIP text tower (mdd_text_tower_*,
+ * mdd_op_attention_causal, mdd_op_token_embed, mdd_op_eot_gather).  A binding built against another version must refuse to
+ * load. */
 #define MDD_ABI_VERSION 13
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
@@ -529,6 +531,53 @@ int mdd_op_softmax_bwd(int dtype, int64_t rows, int cols, int ld, float scale, c
                        const void* dp, const void* dp_t, void* ds, void* ds_t, void* stream);
 int mdd_op_bgemm(int dtype, int a_is_f32, int c_is_f32, const mdd_bgemm_desc* d, const void* A, const void* A_t,
                  const void* B, const void* B_t, void* C, void* C_t, void* stream);
+
+/* ---- the frozen text tower that writes the caption caches (csrc/text_tower.hip, csrc/attn_causal.hip; DESIGN.md section
+ * 13): OpenAI CLIP's encode_text (clip/model.py), which the reference reaches through textprocess / textprocess_train
+ * (networks.py:700-726, distill.py:107-144) for --text_encoder clip.  Forward only.
+ *
+ * Causal multi-head attention, head dimension 64, 1 <= tokens <= 128: qkv is the fused [n, tokens, 3, heads, 64] tensor,
+ * out [n, tokens, heads, 64], both in the storage type (dtype = MDD_DTYPE_F32: exact fp32 FMA; MDD_DTYPE_BF16: bf16 matrix
+ * cores, maximum / denominator / accumulation in fp32).  out[i] = softmax(scale * q_i . K[0..i]) V[0..i]: keys after the
+ * query are never part of the maximum, the denominator or the sum.  Nothing of size tokens x tokens leaves the CU. */
+int mdd_op_attention_causal(int dtype, int n, int tokens, int heads, float scale, const void* qkv, void* out, void* stream);
+/* out[r, t, :] = table[clamp(ids[r, t], 0, vocab - 1), :] + pos[t, :], summed in fp32 and stored in the storage type.
+ * ids int32 [n, ctx] (device), table [vocab, width] and pos [ctx, width] fp32; width a multiple of the 16-byte chunk of
+ * dtype.  The clamp keeps every read inside the table; refusing such ids is the caller's job. */
+int mdd_op_token_embed(int dtype, int n, int ctx, int width, int vocab, const int32_t* ids, const float* table,
+                       const float* pos, void* out, void* stream);
+/* out [n, width] fp32 = x[r, e_r, :] (+ b[r, e_r, :] when b is given, added in fp32), e_r = the FIRST position of the
+ * largest id of row r (torch.argmax; CLIP's end-of-text token has the largest id).  x, b [n, ctx, width] in the storage
+ * type. */
+int mdd_op_eot_gather(int dtype, int n, int ctx, int width, const int32_t* ids, const void* x, const void* b, float* out,
+                      void* stream);
+
+typedef struct mdd_text_tower mdd_text_tower;
+typedef struct mdd_text_tower_config {
+  const char* variant; /* "clip_text_b32" | "clip_text_micro" | "clip_text_nano" */
+  int32_t max_batch;   /* sequences per mdd_text_tower_encode call                                  */
+  int32_t dtype;       /* MDD_DTYPE_F32 | MDD_DTYPE_BF16: storage and arithmetic of the blocks       */
+} mdd_text_tower_config;
+/* create makes no GPU call: a tower that is only asked for its tables works without a GPU */
+int mdd_text_tower_create(const mdd_text_tower_config* cfg, mdd_text_tower** out);
+void mdd_text_tower_destroy(mdd_text_tower* t);
+/* the tower's own flat fp32 parameter vector: names as the `clip` package registers them, under "model."; weights are
+ * matched BY NAME (the flat order is this table's, not that of any whole-CLIP parameter list) */
+int64_t mdd_text_tower_param_numel(const mdd_text_tower* t);
+int mdd_text_tower_param_count(const mdd_text_tower* t);
+int mdd_text_tower_param_info(const mdd_text_tower* t, int index, char* name, int name_cap, int64_t* shape4, int* ndim,
+                              int64_t* offset);
+int mdd_text_tower_feature_dim(const mdd_text_tower* t);
+int mdd_text_tower_context(const mdd_text_tower* t);
+int mdd_text_tower_vocab(const mdd_text_tower* t);
+int64_t mdd_text_tower_workspace_bytes(const mdd_text_tower* t);
+int mdd_text_tower_bind_workspace(mdd_text_tower* t, void* ws_dev, int64_t bytes, void* stream);
+/* theta_dev: the flat fp32 vector of the table above.  The linears are cast and packed and every other parameter is copied
+ * into the workspace here, once: theta_dev is not read after the work enqueued by this call has run. */
+int mdd_text_tower_load(mdd_text_tower* t, const float* theta_dev, void* stream);
+/* ids_dev int32 [n, context], 1 <= n <= max_batch -> out_dev fp32 [n, feature_dim]; enqueues only (no host
+ * synchronisation).  Ids outside [0, vocab) are clamped by the embedding kernel. */
+int mdd_text_tower_encode(mdd_text_tower* t, const int32_t* ids_dev, int n, float* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

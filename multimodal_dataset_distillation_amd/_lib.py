@@ -19,6 +19,10 @@ class MddConfig(C.Structure):
                 ("dtype", C.c_int32), ("keep_steps", C.c_int32)]
 
 
+class MddTextTowerConfig(C.Structure):
+    _fields_ = [("variant", C.c_char_p), ("max_batch", C.c_int32), ("dtype", C.c_int32)]
+
+
 class MddIterArgs(C.Structure):
     _fields_ = [("image_syn", C.c_void_p), ("text_syn", C.c_void_p), ("lr_img", C.c_void_p),
                 ("lr_txt", C.c_void_p), ("theta0_img", C.c_void_p), ("theta0_txt", C.c_void_p),
@@ -111,6 +115,21 @@ SIGNATURES = {
     "mdd_op_softmax": (_I, [_I, _L, _I, _I, _F] + [_P] * 5),
     "mdd_op_softmax_bwd": (_I, [_I, _L, _I, _I, _F] + [_P] * 7),
     "mdd_op_bgemm": (_I, [_I, _I, _I] + [_P] * 8),
+    "mdd_op_attention_causal": (_I, [_I, _I, _I, _I, _F, _P, _P, _P]),
+    "mdd_op_token_embed": (_I, [_I] * 5 + [_P] * 5),
+    "mdd_op_eot_gather": (_I, [_I] * 4 + [_P] * 5),
+    "mdd_text_tower_create": (_I, [C.POINTER(MddTextTowerConfig), C.POINTER(_P)]),
+    "mdd_text_tower_destroy": (None, [_P]),
+    "mdd_text_tower_param_numel": (_L, [_P]),
+    "mdd_text_tower_param_count": (_I, [_P]),
+    "mdd_text_tower_param_info": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_L), C.POINTER(_I), C.POINTER(_L)]),
+    "mdd_text_tower_feature_dim": (_I, [_P]),
+    "mdd_text_tower_context": (_I, [_P]),
+    "mdd_text_tower_vocab": (_I, [_P]),
+    "mdd_text_tower_workspace_bytes": (_L, [_P]),
+    "mdd_text_tower_bind_workspace": (_I, [_P, _P, _L, _P]),
+    "mdd_text_tower_load": (_I, [_P, _P, _P]),
+    "mdd_text_tower_encode": (_I, [_P, _P, _I, _P, _P]),
 }
 
 

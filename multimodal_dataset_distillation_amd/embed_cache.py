@@ -1,14 +1,16 @@
 """Frozen-text-encoder embedding caches and held-out tensors: the on-disk inputs either side of the
 hot path (SURVEY 8b last row, 8f rank 4).
 
-  {dataset}_{text_encoder}_text_embed.npz        key `bert_test_embed`  [n_test_captions, 768]
-  {dataset}_{text_encoder}_train_text_embed.npz  key `bert_test_embed`  [n_train_pairs, 768]
+  {dataset}_{text_encoder}_text_embed.npz        key `bert_test_embed`  [n_test_captions, d_txt]
+  {dataset}_{text_encoder}_train_text_embed.npz  key `bert_test_embed`  [n_train_pairs, d_txt]
 
 are what reference utils.py:872-894 (`load_or_process_file`) reads, written by `textprocess` /
-`textprocess_train` (reference distill.py:107-147).  Producing them needs BERT (outside the MI355X
-path; unavailable offline); READING them needs nothing but numpy, and with them `text_syn` real
-initialisation (reference distill.py:97-105, 228) and the nearest-caption decode (distill.py:89-95,
-244) work end to end.  Files are loaded with allow_pickle=False.
+`textprocess_train` (reference distill.py:107-147).  For `--text_encoder clip` (d_txt 512) this library
+writes them itself: `python -m multimodal_dataset_distillation_amd.embed_text` runs the frozen CLIP text
+tower (text_tower.py) over a file of token ids and stores the result with `write_embed_cache`.  The
+`bert` caches (d_txt 768) still come from the reference: BERT is not built here.  READING either needs
+nothing but numpy, and with them `text_syn` real initialisation (reference distill.py:97-105, 228) and the
+nearest-caption decode (distill.py:89-95, 244) work end to end.  Files are loaded with allow_pickle=False.
 """
 import os
 
@@ -32,8 +34,9 @@ def load_embed_cache(args, file_type, embed_dir=None):
     path = os.path.join(d, name)
     if not os.path.exists(path):
         raise FileNotFoundError(
-            "%s not found: the text-embedding cache is written by the reference's textprocess / "
-            "textprocess_train (distill.py:107-147) with a frozen BERT; this engine only reads it" % path)
+            "%s not found: for --text_encoder clip write it with `python -m multimodal_dataset_distillation_amd."
+            "embed_text`; the bert cache is written by the reference's textprocess / textprocess_train "
+            "(distill.py:107-147) with a frozen BERT, which this library does not build" % path)
     print("Loading %s" % path)
     with np.load(path, allow_pickle=False) as z:
         if EMBED_KEY not in z.files:
@@ -42,6 +45,31 @@ def load_embed_cache(args, file_type, embed_dir=None):
     if arr.ndim != 2:
         raise ValueError("%s: expected a [n, d] array, got shape %s" % (path, arr.shape))
     return torch.from_numpy(arr)
+
+
+def write_embed_cache(args_or_names, file_type, array, embed_dir=None):
+    """What the reference's textprocess / textprocess_train store (distill.py:121, 141): `array` [n, d] as float32
+    under the key `bert_test_embed` in `embed_cache_filename(...)`.  args_or_names: an object with .dataset and
+    .text_encoder (and optionally .embed_dir), or a (dataset, text_encoder) pair.  Returns the path written;
+    `load_embed_cache` reads the same array back."""
+    if isinstance(args_or_names, (tuple, list)):
+        dataset, text_encoder = args_or_names
+        d = embed_dir
+    else:
+        dataset, text_encoder = args_or_names.dataset, args_or_names.text_encoder
+        d = embed_dir if embed_dir is not None else getattr(args_or_names, "embed_dir", None)
+    if file_type not in ("text", "train_text"):
+        raise ValueError("file_type must be 'text' or 'train_text', got %r" % (file_type,))
+    if torch.is_tensor(array):
+        array = array.detach().cpu().numpy()
+    arr = np.ascontiguousarray(array, dtype=np.float32)
+    if arr.ndim != 2:
+        raise ValueError("expected a [n, d] array, got shape %s" % (arr.shape,))
+    d = d or "."
+    os.makedirs(d, exist_ok=True)
+    path = os.path.join(d, embed_cache_filename(dataset, text_encoder, file_type))
+    np.savez(path, **{EMBED_KEY: arr})
+    return path
 
 
 def load_tensor_file(path, key=None):
