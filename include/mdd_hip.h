@@ -73,8 +73,10 @@ const char* mdd_last_error(void);
  * in-engine dropout masks (mdd_iter_args.drop_p / drop_iteration / drop_seed, mdd_txt_forward_rng, mdd_op_dropout_mask,
  * mdd_sizeof_iter_args); still 13 (new symbols only, no struct changed): + mdd_op_quick_gelu / mdd_op_quick_gelu_bwd and the
  * CLIP ViT variants; still 13 (new symbols only, no struct changed): + the frozen CLIP text tower (mdd_text_tower_*,
- * mdd_op_attention_causal, mdd_op_token_embed, mdd_op_eot_gather).  A binding built against another version must refuse to
- * load. */
+ * mdd_op_attention_causal, mdd_op_token_embed, mdd_op_eot_gather); still 13: + the frozen BERT text tower over packed
+ * sequences (mdd_text_tower_encode_varlen, mdd_op_attention_varlen, mdd_op_bert_embed).  mdd_text_tower_config gained
+ * max_tokens at its end: a binding compares mdd_sizeof_text_tower_config() with its own struct, as it does
+ * mdd_sizeof_iter_args().  A binding built against another version must refuse to load. */
 #define MDD_ABI_VERSION 13
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
@@ -532,9 +534,11 @@ int mdd_op_softmax_bwd(int dtype, int64_t rows, int cols, int ld, float scale, c
 int mdd_op_bgemm(int dtype, int a_is_f32, int c_is_f32, const mdd_bgemm_desc* d, const void* A, const void* A_t,
                  const void* B, const void* B_t, void* C, void* C_t, void* stream);
 
-/* ---- the frozen text tower that writes the caption caches (csrc/text_tower.hip, csrc/attn_causal.hip; DESIGN.md section
- * 13): OpenAI CLIP's encode_text (clip/model.py), which the reference reaches through textprocess / textprocess_train
- * (networks.py:700-726, distill.py:107-144) for --text_encoder clip.  Forward only.
+/* ---- the frozen text towers that write the caption caches (csrc/text_tower.hip, csrc/attn_causal.hip,
+ * csrc/attn_varlen.hip; DESIGN.md sections 13 and 14), which the reference reaches through textprocess /
+ * textprocess_train (networks.py:700-735, distill.py:107-144): OpenAI CLIP's encode_text (clip/model.py) for
+ * --text_encoder clip, and transformers' BertModel("bert-base-uncased") -> last_hidden_state[:, 0] for --text_encoder bert
+ * (the default), computed over PACKED sequences: total = sum(len) token rows and cu_seqlens, no padding row.  Forward only.
  *
  * Causal multi-head attention, head dimension 64, 1 <= tokens <= 128: qkv is the fused [n, tokens, 3, heads, 64] tensor,
  * out [n, tokens, heads, 64], both in the storage type (dtype = MDD_DTYPE_F32: exact fp32 FMA; MDD_DTYPE_BF16: bf16 matrix
@@ -552,22 +556,48 @@ int mdd_op_token_embed(int dtype, int n, int ctx, int width, int vocab, const in
 int mdd_op_eot_gather(int dtype, int n, int ctx, int width, const int32_t* ids, const void* x, const void* b, float* out,
                       void* stream);
 
+/* Bidirectional multi-head attention over packed sequences of different lengths (BERT's key-padding mask without the
+ * padding), head dimension 64: qkv [total, 3, heads, 64], out [total, heads, 64] in the storage type; cu_seqlens int32
+ * [n + 1] on the device, cu[0] = 0, cu[n] = total, 1 <= len_r = cu[r + 1] - cu[r] <= max_len <= 512.
+ * out[cu[r] + i] = softmax(scale * q_i . K_r) V_r over the keys of sequence r only: the keys of other sequences are never
+ * loaded, and the LDS rows beyond len_r take no part in the maximum or the denominator (their probabilities are exact
+ * zeros).  K and V are streamed through LDS in stages of 128 keys: the LDS of a workgroup does not depend on max_len.
+ * dtype as for mdd_op_attention_causal.  Whatever cu_seqlens holds, no row outside [0, total) is read or written (the
+ * kernel clamps; a length above max_len is cut to max_len). */
+int mdd_op_attention_varlen(int dtype, int n, int total, int heads, float scale, const void* qkv, const int32_t* cu_seqlens,
+                            int max_len, void* out, void* stream);
+/* BERT's embedding sum over packed rows, before its LayerNorm: out[row, :] = (word[id, :] + pos[t, :]) + type0[:] in fp32,
+ * stored in the storage type (one rounding); id = clamp(ids[row], 0, vocab - 1), t = clamp(row - cu[r], 0, positions - 1)
+ * for the sequence r that holds the row.  ids int32 [total], cu_seqlens int32 [n + 1] (device); word [vocab, width], pos
+ * [positions, width], type0 [width] (row 0 of the token-type table) fp32; width a multiple of the 16-byte chunk. */
+int mdd_op_bert_embed(int dtype, int n, int total, int width, int vocab, int positions, const int32_t* ids,
+                      const int32_t* cu_seqlens, const float* word, const float* pos, const float* type0, void* out,
+                      void* stream);
+
 typedef struct mdd_text_tower mdd_text_tower;
 typedef struct mdd_text_tower_config {
-  const char* variant; /* "clip_text_b32" | "clip_text_micro" | "clip_text_nano" */
-  int32_t max_batch;   /* sequences per mdd_text_tower_encode call                                  */
+  const char* variant; /* "clip_text_b32" | "clip_text_micro" | "clip_text_nano" |
+                          "bert_base_uncased" | "bert_micro" | "bert_nano" */
+  int32_t max_batch;   /* sequences per mdd_text_tower_encode / _encode_varlen call                 */
   int32_t dtype;       /* MDD_DTYPE_F32 | MDD_DTYPE_BF16: storage and arithmetic of the blocks       */
+  int32_t max_tokens;  /* BERT: packed token rows per call, which the workspace is planned from; 0 = max_batch *
+                          context.  The CLIP variants compute whole contexts and ignore it.          */
 } mdd_text_tower_config;
+size_t mdd_sizeof_text_tower_config(void);   /* sizeof(mdd_text_tower_config) of the library */
 /* create makes no GPU call: a tower that is only asked for its tables works without a GPU */
 int mdd_text_tower_create(const mdd_text_tower_config* cfg, mdd_text_tower** out);
 void mdd_text_tower_destroy(mdd_text_tower* t);
-/* the tower's own flat fp32 parameter vector: names as the `clip` package registers them, under "model."; weights are
- * matched BY NAME (the flat order is this table's, not that of any whole-CLIP parameter list) */
+/* the tower's own flat fp32 parameter vector.  CLIP: names as the `clip` package registers them, under "model.".  BERT:
+ * the `transformers` names of BertModel, bare ("embeddings.word_embeddings.weight", "encoder.layer.0.attention.self.
+ * query.weight", ...), every parameter but pooler.* (bert_base_uncased: 108,891,648 elements); a layer's query, key and
+ * value weights (and their biases) lie next to each other, which makes them one [3 D, D] linear.  Weights are matched BY
+ * NAME (the flat order is this table's, not that of any whole-model parameter list) */
 int64_t mdd_text_tower_param_numel(const mdd_text_tower* t);
 int mdd_text_tower_param_count(const mdd_text_tower* t);
 int mdd_text_tower_param_info(const mdd_text_tower* t, int index, char* name, int name_cap, int64_t* shape4, int* ndim,
                               int64_t* offset);
 int mdd_text_tower_feature_dim(const mdd_text_tower* t);
+/* CLIP: the context length every sequence has; BERT: the length of the position table (the longest sequence) */
 int mdd_text_tower_context(const mdd_text_tower* t);
 int mdd_text_tower_vocab(const mdd_text_tower* t);
 int64_t mdd_text_tower_workspace_bytes(const mdd_text_tower* t);
@@ -578,6 +608,13 @@ int mdd_text_tower_load(mdd_text_tower* t, const float* theta_dev, void* stream)
 /* ids_dev int32 [n, context], 1 <= n <= max_batch -> out_dev fp32 [n, feature_dim]; enqueues only (no host
  * synchronisation).  Ids outside [0, vocab) are clamped by the embedding kernel. */
 int mdd_text_tower_encode(mdd_text_tower* t, const int32_t* ids_dev, int n, float* out_dev, void* stream);
+/* BERT towers (a CLIP tower returns "invalid argument", as mdd_text_tower_encode does on a BERT tower): ids_packed_dev
+ * int32 [total] -- the sequences one after another, each starting with its [CLS] token -- and cu_seqlens_dev int32 [n + 1]
+ * as for mdd_op_attention_varlen; 1 <= n <= max_batch, n <= total <= max_tokens, max_len >= the longest sequence and <=
+ * context -> out_dev fp32 [n, feature_dim], the last layer's [CLS] rows (last_hidden_state[:, 0]; the pooler is not part
+ * of the tower).  Enqueues only. */
+int mdd_text_tower_encode_varlen(mdd_text_tower* t, const int32_t* ids_packed_dev, const int32_t* cu_seqlens_dev, int n,
+                                 int total, int max_len, float* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ class MddConfig(C.Structure):
 
 
 class MddTextTowerConfig(C.Structure):
-    _fields_ = [("variant", C.c_char_p), ("max_batch", C.c_int32), ("dtype", C.c_int32)]
+    _fields_ = [("variant", C.c_char_p), ("max_batch", C.c_int32), ("dtype", C.c_int32), ("max_tokens", C.c_int32)]
 
 
 class MddIterArgs(C.Structure):
@@ -118,6 +118,7 @@ SIGNATURES = {
     "mdd_op_attention_causal": (_I, [_I, _I, _I, _I, _F, _P, _P, _P]),
     "mdd_op_token_embed": (_I, [_I] * 5 + [_P] * 5),
     "mdd_op_eot_gather": (_I, [_I] * 4 + [_P] * 5),
+    "mdd_sizeof_text_tower_config": (C.c_size_t, []),
     "mdd_text_tower_create": (_I, [C.POINTER(MddTextTowerConfig), C.POINTER(_P)]),
     "mdd_text_tower_destroy": (None, [_P]),
     "mdd_text_tower_param_numel": (_L, [_P]),
@@ -130,6 +131,9 @@ SIGNATURES = {
     "mdd_text_tower_bind_workspace": (_I, [_P, _P, _L, _P]),
     "mdd_text_tower_load": (_I, [_P, _P, _P]),
     "mdd_text_tower_encode": (_I, [_P, _P, _I, _P, _P]),
+    "mdd_text_tower_encode_varlen": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "mdd_op_attention_varlen": (_I, [_I, _I, _I, _I, _F, _P, _P, _I, _P, _P]),
+    "mdd_op_bert_embed": (_I, [_I] * 6 + [_P] * 7),
 }
 
 
@@ -176,6 +180,9 @@ def load(variant=None):
     if lib.mdd_sizeof_iter_args() != C.sizeof(MddIterArgs):
         raise RuntimeError("libmdd_hip.so mdd_iter_args is %d bytes, this binding's MddIterArgs %d: rebuild (build_ext)"
                            % (lib.mdd_sizeof_iter_args(), C.sizeof(MddIterArgs)))
+    if lib.mdd_sizeof_text_tower_config() != C.sizeof(MddTextTowerConfig):
+        raise RuntimeError("libmdd_hip.so mdd_text_tower_config is %d bytes, this binding's MddTextTowerConfig %d: rebuild "
+                           "(build_ext)" % (lib.mdd_sizeof_text_tower_config(), C.sizeof(MddTextTowerConfig)))
     _lib = lib
     return lib
 

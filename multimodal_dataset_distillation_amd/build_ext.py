@@ -16,7 +16,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmdd_hip.so")
 SOURCES = ["flat_ops.hip", "ws.hip", "elementwise.hip", "linear.hip", "head.hip", "conv_gemm.hip",
            "conv_gemm_relu.hip", "conv_gemm_qgelu.hip", "conv_wgrad.hip", "retrieval.hip", "collective.hip", "vit.hip", "attn.hip",
-           "nfres.hip", "nfreg.hip", "conv_g8.hip", "attn_causal.hip", "text_tower.hip", "ops_abi.hip", "engine.hip"]
+           "nfres.hip", "nfreg.hip", "conv_g8.hip", "attn_causal.hip", "attn_varlen.hip", "text_tower.hip", "ops_abi.hip", "engine.hip"]
 # sources that include another source file: rebuilt when it changes
 INCLUDES = {"conv_gemm_relu.hip": ["conv_gemm.hip"], "conv_gemm_qgelu.hip": ["conv_gemm.hip"]}
 HEADERS = ["common.h", "host.h", "kernels.h", "philox.h", "conv_gemm_epilogue.inc", "conv_gemm_epilogue_se.inc", os.path.join("..", "..", "include", "mdd_hip.h")]

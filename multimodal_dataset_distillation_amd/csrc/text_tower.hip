@@ -1,10 +1,21 @@
-// The frozen text tower that writes the caption caches: OpenAI CLIP's encode_text (clip/model.py), which the reference
-// reaches through textprocess / textprocess_train (networks.py:700-726, distill.py:107-144) for --text_encoder clip.
+// The frozen text towers that write the caption caches, which the reference reaches through textprocess /
+// textprocess_train (networks.py:700-735, distill.py:107-144).
+//
+// --text_encoder clip: OpenAI CLIP's encode_text (clip/model.py).
 //
 //   x = token_embedding[ids] + positional_embedding                     k_token_embed
 //   per block:  x += out_proj(causal_attention(in_proj(ln_1(x))))        k_conv_gemm MODE 0, attn_causal.hip, vit.hip LayerNorm
 //               x += c_proj(QuickGELU(c_fc(ln_2(x))))                    k_conv_gemm with the QuickGELU epilogue
 //   features = ln_final(x[r, argmax ids[r]]) @ text_projection           k_eot_gather, fp32 LayerNorm, small-batch linear
+//
+// --text_encoder bert (the reference's default): transformers' BertModel("bert-base-uncased"), last_hidden_state[:, 0].
+// The tokens stay PACKED -- total = sum(len) rows and cu_seqlens, no padding row anywhere (the reference pads a chunk to
+// its longest caption and computes every padded row):
+//
+//   x = LN_emb(word[id] + position[t] + token_type[0])                   k_bert_embed (t = row - cu[r]), vit.hip LayerNorm
+//   per layer:  x1 = LN(x + dense(attention_varlen(x Wqkv + b)))         one fused [3 D, D] contraction, attn_varlen.hip
+//               x  = LN(x1 + dense(GELU(x1 Wi + b)))                     exact GELU in fc1's epilogue where that instance exists
+//   features[r] = x[cu[r]]                                               k_cls_gather + fp32 LayerNorm on the n [CLS] rows only
 //
 // Forward only, its own handle (mdd_text_tower): no theta tangent, no stash, no backward.  The linears run over n * context
 // token rows on the engine's contraction kernel; a residual sum is formed by the LayerNorm kernel that reads it (and the
@@ -66,19 +77,75 @@ __global__ __launch_bounds__(64) void k_eot_gather(float* __restrict__ out, cons
   for (int c = lane; c < width; c += 64) out[(size_t)r * width + c] = to_f(src[c]) + (src2 ? to_f(src2[c]) : 0.f);
 }
 
+// BERT's embedding sum, packed rows: one thread per 16-byte chunk of the output,
+//   out[row, c ..] = (word[id, c ..] + pos[t, c ..]) + type0[c ..]     fp32, one rounding; t = row - cu[r], cu[r] <= row < cu[r + 1]
+// r is found by bisection in cu_seqlens (n + 1 cached ints); id and t are clamped into their tables
+template <class AT>
+__global__ __launch_bounds__(256) void k_bert_embed(AT* __restrict__ out, const int32_t* __restrict__ ids,
+                                                    const int32_t* __restrict__ cu, const float* __restrict__ word,
+                                                    const float* __restrict__ pos, const float* __restrict__ type0,
+                                                    int64_t chunks, int n, int width, int vocab, int positions) {
+  constexpr int CE = Chunk<AT>::N;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= chunks) return;
+  const int cpr = width / CE;
+  const int64_t row = i / cpr;
+  const int c = (int)(i - row * cpr) * CE;
+  int lo = 0, hi = n;                                        // the last r in [0, n) with cu[r] <= row
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cu[mid] <= row) lo = mid; else hi = mid;
+  }
+  int64_t t = row - cu[lo];
+  t = t < 0 ? 0 : (t >= positions ? positions - 1 : t);     // no position reads outside the table
+  int id = ids[row];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  const float* a = word + (size_t)id * width + c;
+  const float* b = pos + (size_t)t * width + c;
+  float v[CE];
+#pragma unroll
+  for (int e = 0; e < CE; e += 4) {
+    const float4 x = *(const float4*)(a + e), y = *(const float4*)(b + e), z = *(const float4*)(type0 + c + e);
+    v[e] = (x.x + y.x) + z.x; v[e + 1] = (x.y + y.y) + z.y; v[e + 2] = (x.z + y.z) + z.z; v[e + 3] = (x.w + y.w) + z.w;
+  }
+  *(uint4*)(out + row * width + c) = Chunk<AT>::pack(v);
+}
+
+// one wave per sequence: the [CLS] row cu[r] of x (+ b) in fp32; the row is clamped into [0, total)
+template <class AT>
+__global__ __launch_bounds__(64) void k_cls_gather(float* __restrict__ out, const int32_t* __restrict__ cu,
+                                                   const AT* __restrict__ x, const AT* __restrict__ b, int total, int width) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  int at = cu[r];
+  at = at < 0 ? 0 : (at >= total ? total - 1 : at);
+  const AT* src = x + (size_t)at * width;
+  const AT* src2 = b ? b + (size_t)at * width : nullptr;
+  for (int c = lane; c < width; c += 64) out[(size_t)r * width + c] = to_f(src[c]) + (src2 ? to_f(src2[c]) : 0.f);
+}
+
 // ---------------------------------------------------------------------------------------------- spec
 struct TextCfg {
   int vocab, ctx, width, heads, layers, embed;
   float eps = 1e-5f;
-  int act = 4;        // MLP activation (ConvEpi::act): 4 QuickGELU
-  int causal = 1;     // attention mask: 1 causal (CLIP); a key-padding mask is BERT's and not built
-  int post_ln = 0;    // 0: pre-LN residual block (CLIP); 1: post-LN (BERT), not built
+  int act = 4;        // MLP activation (ConvEpi::act): 4 QuickGELU (CLIP), 1 exact GELU (BERT)
+  int causal = 1;     // attention mask: 1 causal over whole contexts (CLIP); 0 BERT's key-padding mask, as packed sequences
+  int post_ln = 0;    // 0: pre-LN residual block (CLIP); 1: post-LN (BERT)
+  int type_vocab = 0; // rows of BERT's token-type table (row 0 is the only one used: the reference passes no token_type_ids)
 };
+bool bert_cfg(TextCfg& c, int vocab, int ctx, int width, int heads, int layers) {
+  c = {vocab, ctx, width, heads, layers, width};            // the feature is the [CLS] row itself
+  c.eps = 1e-12f; c.act = 1; c.causal = 0; c.post_ln = 1; c.type_vocab = 2;
+  return true;
+}
 bool get_text_cfg(const char* v, TextCfg& c) {
   if (!strcmp(v, "clip_text_b32")) { c = {49408, 77, 512, 8, 12, 512}; return true; }   // clip/model.py CLIP(512, ..., 77, 49408, 512, 8, 12)
   // build-defined miniatures (tests): the real context; one row past a 32-row tile with a single head
   if (!strcmp(v, "clip_text_micro")) { c = {512, 77, 128, 2, 2, 24}; return true; }
   if (!strcmp(v, "clip_text_nano")) { c = {64, 33, 64, 1, 2, 8}; return true; }
+  if (!strcmp(v, "bert_base_uncased")) return bert_cfg(c, 30522, 512, 768, 12, 12);        // transformers BertConfig()
+  // build-defined miniatures (tests): the real position table with two heads; 40 positions with a single head
+  if (!strcmp(v, "bert_micro")) return bert_cfg(c, 512, 512, 128, 2, 2);
+  if (!strcmp(v, "bert_nano")) return bert_cfg(c, 64, 40, 64, 1, 2);
   return false;
 }
 
@@ -95,6 +162,7 @@ struct TArena {
 struct mdd_text_tower {
   TextCfg c;
   int max_batch = 0, dtype = 0;
+  int64_t max_tokens = 0;            // token rows the workspace is planned for
   std::vector<TParam> params;
   int64_t P = 0;
   virtual ~mdd_text_tower() {}
@@ -102,6 +170,8 @@ struct mdd_text_tower {
   virtual int bind(void* ws, int64_t bytes, hipStream_t st) = 0;
   virtual int load(const float* theta, hipStream_t st) = 0;
   virtual int encode(const int32_t* ids, int n, float* out, hipStream_t st) = 0;
+  virtual int encode_varlen(const int32_t* ids, const int32_t* cu, int n, int total, int max_len, float* out,
+                            hipStream_t st) = 0;
 };
 
 namespace {
@@ -114,7 +184,7 @@ struct Tower : mdd_text_tower {
   std::vector<LinPackDesc> lpd;
   int lpd_tiles = 0;
   int64_t packed_total = 0, res_total = 0;
-  int64_t r_pos = 0, r_proj = 0, r_tok = 0, r_lnf_w = 0, r_lnf_b = 0;
+  int64_t r_pos = 0, r_proj = 0, r_tok = 0, r_lnf_w = 0, r_lnf_b = 0, r_type = 0;
   bool fused_act = false;
   // workspace
   int64_t ws_bytes = 0, o_res = 0, o_wf = 0, o_lpd = 0, o_un = 0, o_eot = 0, o_hin = 0;
@@ -144,17 +214,36 @@ struct Tower : mdd_text_tower {
     lins.push_back(L);
     return (int)lins.size() - 1;
   }
+  // BERT's query, key and value linears as ONE [3 D, D] contraction: the three weights lie next to each other in the flat
+  // vector (one pack descriptor), and so do the three biases in the resident copy (D is a multiple of its 64-float rows)
+  int add_qkv(const std::string& pre, int D) {
+    TLin L; L.cin = D; L.cout = 3 * D;
+    L.off_w = add_param(pre + "query.weight", {D, D}, false);
+    add_param(pre + "key.weight", {D, D}, false); add_param(pre + "value.weight", {D, D}, false);
+    L.res_b = add_param(pre + "query.bias", {D}, true);
+    add_param(pre + "key.bias", {D}, true); add_param(pre + "value.bias", {D}, true);
+    L.off_p = packed_total; packed_total += (int64_t)3 * D * D;
+    lins.push_back(L);
+    return (int)lins.size() - 1;
+  }
   int build(const mdd_text_tower_config& cfg) {
-    CHECK_ARG(get_text_cfg(cfg.variant, c), "unknown text tower variant (clip_text_b32 | clip_text_micro | clip_text_nano)");
+    CHECK_ARG(get_text_cfg(cfg.variant, c), "unknown text tower variant (clip_text_b32 | clip_text_micro | clip_text_nano | "
+                                            "bert_base_uncased | bert_micro | bert_nano)");
     CHECK_ARG(cfg.max_batch >= 1, "max_batch must be at least 1");
-    CHECK_ARG(c.causal == 1 && c.post_ln == 0 && c.act == 4, "internal: only the pre-LN causal QuickGELU tower (CLIP) is built");
+    CHECK_ARG(cfg.max_tokens >= 0, "max_tokens must not be negative (0 = max_batch * context)");
+    CHECK_ARG((c.causal == 1 && c.post_ln == 0 && c.act == 4) || (c.causal == 0 && c.post_ln == 1 && c.act == 1),
+              "internal: the pre-LN causal QuickGELU tower (CLIP) and the post-LN packed GELU tower (BERT) are built");
     max_batch = cfg.max_batch; dtype = cfg.dtype;
+    // CLIP computes whole contexts: its rows are max_batch * context whatever max_tokens says
+    max_tokens = c.post_ln && cfg.max_tokens > 0 ? cfg.max_tokens : (int64_t)max_batch * c.ctx;
     const int D = c.width, ce = 16 / (int)sizeof(AT);
-    CHECK_ARG(D == c.heads * 64, "internal: the causal attention takes head dimension 64");
-    CHECK_ARG(c.ctx >= 1 && c.ctx <= 128, "internal: the causal attention takes at most 128 tokens");
+    CHECK_ARG(D == c.heads * 64, "internal: the attention kernels take head dimension 64");
+    CHECK_ARG(c.ctx >= 1 && c.ctx <= (c.causal ? 128 : 512), "internal: the causal attention takes at most 128 tokens, the packed one 512");
     CHECK_ARG(D % ce == 0 && D / ce <= 256, "internal: width must be whole 16-byte chunks, at most 256 of them");
     // the contraction kernel indexes its output with 32-bit element offsets
-    CHECK_ARG((int64_t)max_batch * c.ctx * 4 * D < (1ll << 31), "max_batch * context * 4 * width must stay below 2^31 elements");
+    if (c.post_ln) CHECK_ARG(max_tokens * 4 * D < (1ll << 31), "max_tokens * 4 * width must stay below 2^31 elements");
+    else CHECK_ARG((int64_t)max_batch * c.ctx * 4 * D < (1ll << 31), "max_batch * context * 4 * width must stay below 2^31 elements");
+    if (c.post_ln) build_bert_table(); else {
     // the `clip` package's names (CLIP.named_parameters order, the text tower's entries of it), under "model."
     const std::string m = "model.";
     r_pos = add_param(m + "positional_embedding", {c.ctx, D}, true);
@@ -172,6 +261,7 @@ struct Tower : mdd_text_tower {
     }
     r_tok = add_param(m + "token_embedding.weight", {c.vocab, D}, true);
     r_lnf_w = add_param(m + "ln_final.weight", {D}, true); r_lnf_b = add_param(m + "ln_final.bias", {D}, true);
+    }
     int64_t tiles = 0;
     for (auto& L : lins) lpd.push_back(lin_pack_desc(L.cout, L.cin, L.off_w, L.off_p, tiles));
     CHECK_ARG(tiles <= 2147483647ll, "too many tiles");
@@ -179,7 +269,7 @@ struct Tower : mdd_text_tower {
     fused_act = conv_gemm_supports_gelu(geom(lins[blks[0].fc1], 1));
     // ---- workspace plan
     TArena a;
-    const int64_t M = (int64_t)max_batch * c.ctx, es = sizeof(AT);
+    const int64_t M = max_tokens, es = sizeof(AT);
     o_res = a.take(res_total * 4);
     o_wf = a.take(packed_total * es);
     o_lpd = a.take((int64_t)lpd.size() * sizeof(LinPackDesc));
@@ -193,6 +283,28 @@ struct Tower : mdd_text_tower {
     if (a.cur - o_un < packed_total * es) { a.cur = o_un; a.take(packed_total * es); }
     ws_bytes = a.cur;
     return 0;
+  }
+  // transformers' names (BertModel.named_parameters, bare), every parameter but pooler.*; query / key / value adjacent
+  void build_bert_table() {
+    const int D = c.width;
+    const std::string e = "embeddings.";
+    r_tok = add_param(e + "word_embeddings.weight", {c.vocab, D}, true);
+    r_pos = add_param(e + "position_embeddings.weight", {c.ctx, D}, true);
+    r_type = add_param(e + "token_type_embeddings.weight", {c.type_vocab, D}, true);
+    r_lnf_w = add_param(e + "LayerNorm.weight", {D}, true); r_lnf_b = add_param(e + "LayerNorm.bias", {D}, true);   // LN_emb
+    for (int l = 0; l < c.layers; ++l) {
+      const std::string pre = "encoder.layer." + std::to_string(l) + ".";
+      TBlk B;
+      B.qkv = add_qkv(pre + "attention.self.", D);
+      B.proj = add_lin(pre + "attention.output.dense.weight", pre + "attention.output.dense.bias", D, D);
+      B.ln1_w = add_param(pre + "attention.output.LayerNorm.weight", {D}, true);
+      B.ln1_b = add_param(pre + "attention.output.LayerNorm.bias", {D}, true);
+      B.fc1 = add_lin(pre + "intermediate.dense.weight", pre + "intermediate.dense.bias", D, 4 * D);
+      B.fc2 = add_lin(pre + "output.dense.weight", pre + "output.dense.bias", 4 * D, D);
+      B.ln2_w = add_param(pre + "output.LayerNorm.weight", {D}, true);
+      B.ln2_b = add_param(pre + "output.LayerNorm.bias", {D}, true);
+      blks.push_back(B);
+    }
   }
   ConvGeom geom(const TLin& L, int rows) const {
     ConvGeom g; g.nimg = rows; g.ha = 1; g.wa = 1; g.ca_tot = L.cin; g.ho = 1; g.wo = 1; g.co_tot = L.cout; g.kc = L.cin;
@@ -231,6 +343,7 @@ struct Tower : mdd_text_tower {
   }
 #define TT_RC(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
   int encode(const int32_t* ids, int n, float* out, hipStream_t st) override {
+    CHECK_ARG(!c.post_ln, "a BERT tower takes packed sequences: mdd_text_tower_encode_varlen");
     CHECK_ARG(loaded, "mdd_text_tower_load has not run on this workspace");
     CHECK_ARG(ids && out, "null pointer");
     CHECK_ARG(n >= 1 && n <= max_batch, "n must be in [1, max_batch]");
@@ -269,6 +382,44 @@ struct Tower : mdd_text_tower {
     POST_LAUNCH("text_tower_encode");
     return 0;
   }
+  int encode_varlen(const int32_t* ids, const int32_t* cu, int n, int total, int max_len, float* out,
+                    hipStream_t st) override {
+    CHECK_ARG(c.post_ln, "a CLIP tower takes whole contexts: mdd_text_tower_encode");
+    CHECK_ARG(loaded, "mdd_text_tower_load has not run on this workspace");
+    CHECK_ARG(ids && cu && out, "null pointer");
+    CHECK_ARG(n >= 1 && n <= max_batch, "n must be in [1, max_batch]");
+    CHECK_ARG(total >= n && total <= max_tokens, "total must be in [n, max_tokens]");
+    CHECK_ARG(max_len >= 1 && max_len <= c.ctx, "max_len must be in [1, positions]");
+    const int D = c.width, M = total;
+    const float scale = 1.f / std::sqrt(64.f);
+    TT_RC(mdd_op_bert_embed(DT, n, M, D, c.vocab, c.ctx, ids, cu, res + r_tok, res + r_pos, res + r_type, TMP, st));
+    TT_RC(mdd_op_layernorm(DT, M, D, c.eps, TMP, nullptr, res + r_lnf_w, nullptr, res + r_lnf_b, nullptr, X, nullptr, st));
+    for (int l = 0; l < c.layers; ++l) {
+      const TBlk& B = blks[l];
+      lin(lins[B.qkv], M, X, QKV, nullptr, 0, st);
+      TT_RC(mdd_op_attention_varlen(DT, n, M, c.heads, scale, QKV, cu, max_len, O, st));
+      lin(lins[B.proj], M, O, TMP, nullptr, 0, st);
+      // post-LN: the residual sum is normalised in place of being carried (the sum itself, written to Nn, is not read again)
+      TT_RC(mdd_op_add_layernorm(DT, M, D, c.eps, X, nullptr, TMP, nullptr, Nn, nullptr, res + B.ln1_w, nullptr,
+                                 res + B.ln1_b, nullptr, X2, nullptr, st));
+      if (fused_act) lin(lins[B.fc1], M, X2, nullptr, A, c.act, st);
+      else {
+        lin(lins[B.fc1], M, X2, C, nullptr, 0, st);
+        TT_RC(mdd_op_gelu(DT, (int64_t)M * 4 * D, C, nullptr, A, nullptr, st));
+      }
+      lin(lins[B.fc2], M, A, TMP, nullptr, 0, st);
+      if (l + 1 < c.layers)
+        TT_RC(mdd_op_add_layernorm(DT, M, D, c.eps, X2, nullptr, TMP, nullptr, Nn, nullptr, res + B.ln2_w, nullptr,
+                                   res + B.ln2_b, nullptr, X, nullptr, st));
+    }
+    // the last layer's residual sum and LayerNorm in fp32 on the n [CLS] rows only (LayerNorm is per row)
+    const TBlk& L = blks[c.layers - 1];
+    k_cls_gather<AT><<<(unsigned)n, 64, 0, st>>>(eot, cu, X2, TMP, M, D);
+    TT_RC(mdd_op_layernorm(MDD_DTYPE_F32, n, D, c.eps, eot, nullptr, res + L.ln2_w, nullptr, res + L.ln2_b, nullptr, out,
+                           nullptr, st));
+    POST_LAUNCH("text_tower_encode_varlen");
+    return 0;
+  }
 #undef TT_RC
 };
 
@@ -293,6 +444,25 @@ int mdd_op_token_embed(int dtype, int n, int ctx, int width, int vocab, const in
   return 0;
 }
 
+int mdd_op_bert_embed(int dtype, int n, int total, int width, int vocab, int positions, const int32_t* ids,
+                      const int32_t* cu_seqlens, const float* word, const float* pos, const float* type0, void* out,
+                      void* stream) {
+  CHECK_STORAGE(dtype);
+  CHECK_ARG(n >= 1 && total >= n && width >= 1 && vocab >= 1 && positions >= 1, "empty problem");
+  CHECK_ARG(ids && cu_seqlens && word && pos && type0 && out, "null pointer");
+  const int ce = dtype == MDD_DTYPE_F32 ? 4 : 8;
+  CHECK_ARG(width % ce == 0, "width must be a multiple of the 16-byte chunk");
+  const int64_t chunks = (int64_t)total * (width / ce);
+  CHECK_ARG((chunks + 255) / 256 <= 2147483647ll, "too many rows");
+  with_storage(dtype, [&](auto* tag) {
+    using AT = tag_t<decltype(tag)>;
+    k_bert_embed<AT><<<(unsigned)((chunks + 255) / 256), 256, 0, (hipStream_t)stream>>>((AT*)out, ids, cu_seqlens, word, pos,
+                                                                                        type0, chunks, n, width, vocab, positions);
+  });
+  POST_LAUNCH("op_bert_embed");
+  return 0;
+}
+
 int mdd_op_eot_gather(int dtype, int n, int ctx, int width, const int32_t* ids, const void* x, const void* b, float* out,
                       void* stream) {
   CHECK_STORAGE(dtype);
@@ -305,6 +475,7 @@ int mdd_op_eot_gather(int dtype, int n, int ctx, int width, const int32_t* ids, 
   return 0;
 }
 
+size_t mdd_sizeof_text_tower_config(void) { return sizeof(mdd_text_tower_config); }
 int mdd_text_tower_create(const mdd_text_tower_config* cfg, mdd_text_tower** out) {
   CHECK_ARG(cfg && out && cfg->variant, "null config");
   *out = nullptr;
@@ -346,6 +517,12 @@ int mdd_text_tower_load(mdd_text_tower* t, const float* theta_dev, void* stream)
 int mdd_text_tower_encode(mdd_text_tower* t, const int32_t* ids_dev, int n, float* out_dev, void* stream) {
   CHECK_ARG(t, "null tower");
   return t->encode(ids_dev, n, out_dev, (hipStream_t)stream);
+}
+
+int mdd_text_tower_encode_varlen(mdd_text_tower* t, const int32_t* ids_packed_dev, const int32_t* cu_seqlens_dev, int n,
+                                 int total, int max_len, float* out_dev, void* stream) {
+  CHECK_ARG(t, "null tower");
+  return t->encode_varlen(ids_packed_dev, cu_seqlens_dev, n, total, max_len, out_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -5,10 +5,10 @@ hot path (SURVEY 8b last row, 8f rank 4).
   {dataset}_{text_encoder}_train_text_embed.npz  key `bert_test_embed`  [n_train_pairs, d_txt]
 
 are what reference utils.py:872-894 (`load_or_process_file`) reads, written by `textprocess` /
-`textprocess_train` (reference distill.py:107-147).  For `--text_encoder clip` (d_txt 512) this library
-writes them itself: `python -m multimodal_dataset_distillation_amd.embed_text` runs the frozen CLIP text
-tower (text_tower.py) over a file of token ids and stores the result with `write_embed_cache`.  The
-`bert` caches (d_txt 768) still come from the reference: BERT is not built here.  READING either needs
+`textprocess_train` (reference distill.py:107-147).  For `--text_encoder clip` (d_txt 512) and
+`--text_encoder bert` (d_txt 768, the default) this library writes them itself: `python -m
+multimodal_dataset_distillation_amd.embed_text` runs the frozen CLIP or BERT text tower (text_tower.py) over a
+file of token ids and stores the result with `write_embed_cache`.  READING either needs
 nothing but numpy, and with them `text_syn` real initialisation (reference distill.py:97-105, 228) and the
 nearest-caption decode (distill.py:89-95, 244) work end to end.  Files are loaded with allow_pickle=False.
 """
@@ -34,9 +34,9 @@ def load_embed_cache(args, file_type, embed_dir=None):
     path = os.path.join(d, name)
     if not os.path.exists(path):
         raise FileNotFoundError(
-            "%s not found: for --text_encoder clip write it with `python -m multimodal_dataset_distillation_amd."
-            "embed_text`; the bert cache is written by the reference's textprocess / textprocess_train "
-            "(distill.py:107-147) with a frozen BERT, which this library does not build" % path)
+            "%s not found: write it with `python -m multimodal_dataset_distillation_amd.embed_text --text_encoder "
+            "clip|bert` (the reference's textprocess / textprocess_train, distill.py:107-147, with the frozen CLIP or "
+            "BERT text tower)" % path)
     print("Loading %s" % path)
     with np.load(path, allow_pickle=False) as z:
         if EMBED_KEY not in z.files:
