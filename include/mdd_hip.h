@@ -76,7 +76,8 @@ const char* mdd_last_error(void);
  * mdd_op_attention_causal, mdd_op_token_embed, mdd_op_eot_gather); still 13: + the frozen BERT text tower over packed
  * sequences (mdd_text_tower_encode_varlen, mdd_op_attention_varlen, mdd_op_bert_embed).  mdd_text_tower_config gained
  * max_tokens at its end: a binding compares mdd_sizeof_text_tower_config() with its own struct, as it does
- * mdd_sizeof_iter_args().  A binding built against another version must refuse to load. */
+ * mdd_sizeof_iter_args(); still 13 (new symbol only): + mdd_set_skip_unused_param_grads.  A binding built against
+ * another version must refuse to load. */
 #define MDD_ABI_VERSION 13
 int mdd_version(void);
 /* The wide bf16 pointwise contractions (>= 768 channels in and out, >= 8192 rows: the ViT linears) run on 256 x 256-tile
@@ -93,6 +94,12 @@ int mdd_set_group8_kernels(int enable);
  * the previous setting).  Both give the same bits in the forward passes.  For the parity tests, which run a pass both
  * ways, and for A/B timing. */
 int mdd_set_se_fused(int enable);
+/* mdd_unrolled_match does not compute the parameter gradients that nothing reads (1, the default): the Hessian-vector
+ * product of reverse step 0, after which lambda is dead, and the inner gradient of a step the stash policy recomputes,
+ * whose g_k is kept from the forward sweep.  The data gradients of those passes run launch for launch as before.  0 = every
+ * backward pass computes its parameter gradients (process-wide; returns the previous setting).  The op-level entry points
+ * (mdd_img_backward, mdd_img_tangent_backward, mdd_txt_*) always compute them.  For the parity tests and for A/B timing. */
+int mdd_set_skip_unused_param_grads(int enable);
 
 /* ---- engine lifetime and memory (the caller owns device memory: PyTorch caching allocator) */
 int mdd_engine_create(const mdd_config* cfg, mdd_engine** out);

@@ -84,6 +84,7 @@ SIGNATURES = {
     "mdd_set_pipe_kernels": (_I, [_I]),
     "mdd_set_group8_kernels": (_I, [_I]),
     "mdd_set_se_fused": (_I, [_I]),
+    "mdd_set_skip_unused_param_grads": (_I, [_I]),
     "mdd_op_conv2d_wgrad2": (_I, [_I] * 10 + [_P] * 7 + [C.c_longlong, _P]),
     "mdd_op_maxpool2d_3s2": (_I, [_I] * 6 + [_P] * 4),
     "mdd_op_mid_se": (_I, [_I] * 5 + [_F] + [_P] * 12),

@@ -31,6 +31,10 @@ static thread_local std::string g_err;
 // mdd_set_se_fused: the squeeze-excite apply in conv3's forward epilogue (NFNet walker)
 static std::atomic<int> g_se_fused{1};
 static bool se_fused_enabled() { return g_se_fused.load(std::memory_order_relaxed) != 0; }
+// mdd_set_skip_unused_param_grads: mdd_unrolled_match runs the backward passes whose parameter gradients nothing reads
+// (the tangent backward of reverse step 0, the inner backward of a recomputed step) in the walkers' no_pgrad mode
+static std::atomic<int> g_skip_unused{1};
+static bool skip_unused_enabled() { return g_skip_unused.load(std::memory_order_relaxed) != 0; }
 int mdd_set_error(hipError_t e, const char* what) {
   char buf[512];
   snprintf(buf, sizeof buf, "HIP error %d (%s) at %s%s", (int)e, hipGetErrorString(e), what,
@@ -324,6 +328,11 @@ struct Eng : mdd_engine {
   float* lossw = nullptr;
   // unrolled-match state
   std::vector<float*> thI, thT, gI, gT;    // theta_k (k=1..K), g_k
+  // Packed weight gradient (dwf) of every step that shares the recompute slot: the tangent pass of step k differentiates
+  // the weight-standardisation backward, which reads the PRIMAL dwf of step k.  With one buffer per such step the forward
+  // sweep's dwf outlives the slot's reuse, and the recompute of the step need not run its weight gradients again
+  // ([keep] is the slot's own buffer, the others are planned beside g_k; the ViT has no packed gradient).
+  std::vector<float*> dwfK;
   float *lamI, *lamT, *nuI, *nuT, *hI, *hT;
   float *fx_t, *fy_t, *xbar, *ybar, *xbar_t, *ybar_t, *sbar, *sbar_t;
   double* dsc;                              // [0..3] sqdist, [4],[5] dlr
@@ -739,6 +748,8 @@ struct Eng : mdd_engine {
     thI.assign(K + 1, nullptr); thT.assign(K + 1, nullptr); gI.assign(K, nullptr); gT.assign(K, nullptr);
     for (int k = 1; k <= K; ++k) { plan(&thI[k], P_img, nullptr, -2); plan(&thT[k], P_txt, nullptr, -2); }
     for (int k = 0; k < K; ++k) { plan(&gI[k], P_img, nullptr, -2); plan(&gT[k], P_txt, nullptr, -2); }
+    dwfK.assign(K, nullptr);
+    if (!is_vit) for (int k = keep + 1; k < K; ++k) plan(&dwfK[k], packed_total, nullptr, -2);
     plan(&lamI, P_img, nullptr, -2); plan(&lamT, P_txt, nullptr, -2);
     plan(&nuI, P_img, nullptr, -2); plan(&nuT, P_txt, nullptr, -2);
     plan(&hI, P_img, nullptr, -2); plan(&hT, P_txt, nullptr, -2);
@@ -775,6 +786,7 @@ struct Eng : mdd_engine {
     DevGuard guard(device_id);
     base = (char*)ws;
     for (auto& f : fix) *f.first = (void*)(base + f.second);
+    if (!is_vit && keep < K) dwfK[keep] = sets[keep].dwf;
     d_descs = (WsDesc*)(base + o_descs);
     if (!descs.empty())
       HIP_CHECK_RET(hipMemcpyAsync(d_descs, descs.data(), descs.size() * sizeof(WsDesc),
@@ -976,6 +988,20 @@ struct Eng : mdd_engine {
   // these results before the end of the pass.
   static constexpr bool MAIN_TAIL = true;
   std::vector<std::function<void(hipStream_t)>> wq;
+  // "No parameter gradient" mode of the backward walkers (img_backward / txt_backward): every launch whose only outputs
+  // are parameter gradients is dropped at its emission point -- the weight gradients and their combines, the small-batch
+  // linears' weight gradients, the weight-standardisation backward.  The data gradients read none of what those launches
+  // write, so they are launch for launch what they are without the mode; kernels that produce a data gradient and a
+  // parameter gradient together (LayerNorm backward, the ViT embedding backward) still run and still write into gout.
+  // Only unrolled_match sets it, through NoPgrad below, so that every return path clears it again.
+  bool no_pgrad = false;
+  struct NoPgrad {
+    bool& flag; const bool prev;
+    NoPgrad(bool& f, bool on) : flag(f), prev(f) { flag = on; }
+    ~NoPgrad() { flag = prev; }
+    NoPgrad(const NoPgrad&) = delete;
+    NoPgrad& operator=(const NoPgrad&) = delete;
+  };
   // wide pointwise layers (the ViT linears) queued since the last flush: launched together, up to four per launch
   // (csrc/conv_wgrad.hip launch_conv_wgrad_group: a layer's 108 tiles need two pixel chunks instead of seven)
   struct WgQ { const ConvL* L; WgradItem it; };
@@ -1015,6 +1041,7 @@ struct Eng : mdd_engine {
   // weight + bias gradient of conv L (dy = grad wrt its raw output, x = its input)
   void conv_bwd_w(bool T, const ConvL& L, const AT* dy, const AT* dy_t, const AT* x, const AT* x_t,
                   float* dwf_, float* dwf_t_, float* gout, hipStream_t) {
+    if (no_pgrad) return;   // neither queue gets an entry: a flush_w with nothing queued returns before its fork
     const ConvL* Lp = &L;
     float* const dbias = L.off_b >= 0 ? gout + L.off_b : nullptr;   // a bias-free layer (CLIP's conv1): no bias gradient
     // the wide pointwise layers queued between two flushes share one weight-gradient launch
@@ -1071,6 +1098,7 @@ struct Eng : mdd_engine {
   // the weight gradient of a linear goes to gout + off_w: conv_bwd_w adds the layer's PACKED offset to its base
   void lin_bwd_w(bool T, const ConvL& L, const AT* dy, const AT* dy_t, const AT* x, const AT* x_t, float* gout,
                  hipStream_t st) {
+    if (no_pgrad) return;
     float* basep = gout + (L.off_w - L.off_p);
     conv_bwd_w(T, L, dy, dy_t, x, x_t, basep, basep, gout, st);
   }
@@ -1239,8 +1267,9 @@ struct Eng : mdd_engine {
     } else if (vit.proj > 0) {
       // dproj [dim, proj] = hin^T ybar (the weight-gradient form with its operands exchanged, no bias gradient);
       // dhin = ybar proj^T (the forward form)
-      launch_linear_wgrad(gout + off_proj, nullptr, P.hin, T ? Q.hin : nullptr, O.yB, T ? ybar_t_in : nullptr, N, vit.proj, D,
-                          lin_main, st);
+      if (!no_pgrad)
+        launch_linear_wgrad(gout + off_proj, nullptr, P.hin, T ? Q.hin : nullptr, O.yB, T ? ybar_t_in : nullptr, N, vit.proj, D,
+                            lin_main, st);
       launch_linear_fwd(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_proj, tp(T, th_t + off_proj),
                         nullptr, nullptr, N, vit.proj, D, 0, lin_main, st);
       if (!cls_hi) launch_f32_to_act<AT>(T ? Q.CLSNB : O.CLSNB, T ? Q.hinB : O.hinB, (int64_t)N * D, st);
@@ -1401,6 +1430,7 @@ struct Eng : mdd_engine {
   // value and asks for the split-K scratch of the stream it runs on when it runs.
   void queue_se_wgrads(bool T, const Blk& B, BlockActs& oa, BlockActs& pa, BlockActs& qa, const float* in,
                        const float* in_t, float* gout) {
+    if (no_pgrad) return;
     const float *zB = oa.zB, *zB_t = T ? qa.zB : nullptr, *hh = pa.h, *hh_t = T ? qa.h : nullptr;
     const float *hB = oa.hB, *hB_t = T ? qa.hB : nullptr, *ii = in, *ii_t = T ? in_t : nullptr;
     float *gw2 = gout + B.se.off_w2, *gb2 = gout + B.se.off_b2, *gw1 = gout + B.se.off_w1, *gb1 = gout + B.se.off_b1;
@@ -1427,8 +1457,9 @@ struct Eng : mdd_engine {
   }
   void classifier_bwd(bool T, ActSet& P, ActSet& Q, ActSet& O, int in, int out, const float* ybar_t_in, float* gout,
                       const float* th, const float* th_t, hipStream_t st) {
-    launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N, in, out,
-                        lin_main, st);
+    if (!no_pgrad)
+      launch_linear_wgrad(gout + off_hw, gout + off_hb, O.yB, T ? ybar_t_in : nullptr, P.hin, T ? Q.hin : nullptr, N, in, out,
+                          lin_main, st);
     launch_linear_dgrad(O.hinB, T ? Q.hinB : nullptr, O.yB, T ? ybar_t_in : nullptr, th + off_hw, tp(T, th_t + off_hw),
                         nullptr, N, in, out, lin_main, st);
   }
@@ -1506,7 +1537,9 @@ struct Eng : mdd_engine {
   int walk_bwd_end(bool T, float* dw, float* dw_t, float* gout, const float* th, const float* th_t, hipStream_t st) {
     flush_w(st, MAIN_TAIL);
     join(st);
-    launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw, T ? dw_t : nullptr, gout, st);
+    // (no_pgrad: nothing was queued and the packed gradient dw was not written)
+    if (!no_pgrad)
+      launch_ws_backward(d_descs, (int)descs.size(), total_rows, th, T ? th_t : nullptr, dw, T ? dw_t : nullptr, gout, st);
     POST_WALK();
     return 0;
   }
@@ -1773,7 +1806,8 @@ struct Eng : mdd_engine {
         const int n_ = N, mid_ = B.mid;
         // the pooled path's share of conv3's weight gradient, after conv3's own weight gradient (queued above: same
         // stream, in order) has overwritten its slice
-        wq.push_back([=](hipStream_t ws_) { launch_linear_wgrad_accum(gw3, gb3, pB, pB_t, qq, qq_t, n_, mid_, c, ws_); });
+        if (!no_pgrad)
+          wq.push_back([=](hipStream_t ws_) { launch_linear_wgrad_accum(gw3, gb3, pB, pB_t, qq, qq_t, n_, mid_, c, ws_); });
       }
       se_mlp_bwd(T, B, oa, pa, qa, oa.pB, qa.pB, th, th_t, st);
       launch_linear_fwd_w<AT>(oa.qB, T ? qa.qB : nullptr, oa.pB, T ? qa.pB : nullptr, wt + L3.off_p,
@@ -1902,14 +1936,16 @@ struct Eng : mdd_engine {
     launch_ln_bwd(O.trB, T ? Q.trB : nullptr, O.tfB, T ? Q.tfB : nullptr, gout + t_lw, gout + t_lb,
                   ln_stats, O.tyB, T ? ybar_t_in : nullptr, P.tr, T ? Q.tr : nullptr,
                   slot_drop_[slot].mask, slot_drop_[slot].spec, th + t_lw, tt(t_lw), N, feat, 1e-5f, st);
-    launch_linear_wgrad(gout + t_fw, gout + t_fb, O.tfB, T ? Q.tfB : nullptr, P.tg,
-                        T ? Q.tg : nullptr, N, feat, feat, lin_txt, st);
+    if (!no_pgrad)
+      launch_linear_wgrad(gout + t_fw, gout + t_fb, O.tfB, T ? Q.tfB : nullptr, P.tg,
+                          T ? Q.tg : nullptr, N, feat, feat, lin_txt, st);
     launch_linear_dgrad(O.tgB, T ? Q.tgB : nullptr, O.tfB, T ? Q.tfB : nullptr, th + t_fw, tt(t_fw),
                         nullptr, N, feat, feat, lin_txt, st);
     launch_gelu_bwd(O.tpB, T ? Q.tpB : nullptr, O.trB, T ? Q.trB : nullptr, O.tgB,
                     T ? Q.tgB : nullptr, P.tp, T ? Q.tp : nullptr, (int64_t)N * feat, st);
-    launch_linear_wgrad(gout + t_pw, gout + t_pb, O.tpB, T ? Q.tpB : nullptr, P.tx, nullptr, N, Dt,
-                        feat, lin_txt, st);
+    if (!no_pgrad)
+      launch_linear_wgrad(gout + t_pw, gout + t_pb, O.tpB, T ? Q.tpB : nullptr, P.tx, nullptr, N, Dt,
+                          feat, lin_txt, st);
     if (dtext) {
       float* xb = T ? Q.txB : O.txB;
       launch_linear_dgrad(O.txB, T ? Q.txB : nullptr, O.tpB, T ? Q.tpB : nullptr, th + t_pw,
@@ -1947,13 +1983,31 @@ struct Eng : mdd_engine {
     const int64_t nfeat = (int64_t)N * feat;
     hipStream_t ts = (use_side && tside) ? tside : st;
     int rc;
+    // parameter gradients nothing reads are not computed (mdd_set_skip_unused_param_grads; read once per iteration)
+    const bool skip_unused = skip_unused_enabled();
+    // steps in the shared slot write / read their own packed weight gradient (dwfK); the slot's own on every return path
+    struct SlotDwf {
+      float*& p; float* const own;
+      explicit SlotDwf(float*& q) : p(q), own(q) {}
+      ~SlotDwf() { p = own; }
+    } slot_dwf(sets[keep < K ? keep : 0].dwf);
+    auto select_dwf = [&](int k) {
+      if (skip_unused && keep < K && k >= keep && dwfK[k]) sets[keep].dwf = dwfK[k];
+    };
     std::vector<const float*> tI(Ks + 1), tT(Ks + 1);
     tI[0] = a->theta0_img; tT[0] = a->theta0_txt;
     for (int k = 1; k <= Ks; ++k) { tI[k] = thI[k]; tT[k] = thT[k]; }
     HIP_CHECK_RET(hipMemsetAsync(dsc, 0, 16 * sizeof(double), st));
     // ---- unrolled student training (distill.py:509-583)
-    // primal forward + contrastive head + inner gradient of step k at theta_k, activations into `slot`
-    auto primal_step = [&](int k, int slot) -> int {
+    // primal forward + contrastive head + inner gradient of step k at theta_k, activations into `slot`.
+    // refill: the reverse sweep's recompute of a step whose activations were not kept.  It runs the inner backward only
+    // for the a-bar / c-bar stash; g_k and the step's packed weight gradient (dwfK) are kept from the forward sweep, so
+    // the two passes run without parameter gradients and are given hI / hT (idle until this step's tangent backward
+    // zero-fills them) for what their fused kernels still write beside a data gradient.
+    auto primal_step = [&](int k, int slot, bool refill) -> int {
+      const bool np = refill && skip_unused;
+      NoPgrad mode(no_pgrad, np);
+      select_dwf(k);
       const int64_t* idx = a->perms ? a->perms + (int64_t)k * N : nullptr;
       const float* mask = a->drop_masks ? a->drop_masks + (int64_t)k * nfeat : nullptr;
       // the engine's own mask is drawn for STEP k, whichever slot holds it: the shared slot's recompute draws it again
@@ -1969,16 +2023,16 @@ struct Eng : mdd_engine {
                             a->logit_scale_const, a->losses + 3 + k, Pk.yB, Pk.tyB, sbar, st)))
         return rc;
       fork_to(ts, st);
-      if ((rc = txt_backward(false, slot, tT[k], nullptr, Pk.tyB, nullptr, gT[k], nullptr, nullptr,
+      if ((rc = txt_backward(false, slot, tT[k], nullptr, Pk.tyB, nullptr, np ? hT : gT[k], nullptr, nullptr,
                              nullptr, 0.f, true, ts))) return rc;
-      if ((rc = img_backward(false, slot, tI[k], nullptr, Pk.yB, nullptr, gI[k], nullptr, nullptr,
+      if ((rc = img_backward(false, slot, tI[k], nullptr, Pk.yB, nullptr, np ? hI : gI[k], nullptr, nullptr,
                              nullptr, 0.f, false, true, st))) return rc;
       return 0;
     };
     int shared_holds = -1;   // which step's activations the shared (recompute) slot currently holds
     for (int k = 0; k < Ks; ++k) {
       const int slot = slot_of(k);
-      if ((rc = primal_step(k, slot))) return rc;
+      if ((rc = primal_step(k, slot, false))) return rc;
       if (slot == keep) shared_holds = k;
       launch_axpy_out(thT[k + 1], tT[k], gT[k], a->lr_txt, -1.f, P_txt, ts);
       launch_axpy_out(thI[k + 1], tI[k], gI[k], a->lr_img, -1.f, P_img, st);
@@ -2000,12 +2054,14 @@ struct Eng : mdd_engine {
       const int slot = slot_of(k);
       if (slot == keep && keep < K && shared_holds != k) {
         // stash policy: this step's activations were not kept -- recompute its forward pass and inner
-        // gradient at the kept theta_k into the shared slot (3 of the 12 contractions this step then costs)
+        // gradient at the kept theta_k into the shared slot (3 of the 12 contractions this step then costs; 2 of 11
+        // with the weight gradients of the refill skipped)
         join_from(ts, st);
-        if ((rc = primal_step(k, slot))) return rc;
+        if ((rc = primal_step(k, slot, true))) return rc;
         shared_holds = k;
       }
       ActSet& Pk = sets[slot];
+      select_dwf(k);
       fork_to(ts, st);
       launch_dot(gT[k], lamT, dsc + 5, -1.0, P_txt, ts);
       launch_scale_out(nuT, lamT, a->lr_txt, 1.f, P_txt, ts);
@@ -2017,13 +2073,16 @@ struct Eng : mdd_engine {
       if ((rc = contrastive(true, Pk.y, Pk.ty, fx_t, fy_t, scale_dev, a->logit_scale_const,
                             nullptr, xbar_t, ybar_t, sbar_t, st))) return rc;
       fork_to(ts, st);
+      // nothing reads lambda after step 0: its H v is not computed, only the data gradients (and sbar_t, above)
+      const bool last = skip_unused && k == 0;
+      NoPgrad mode(no_pgrad, last);
       if ((rc = txt_backward(true, slot, tT[k], nuT, nullptr, ybar_t, hT, a->grad_text_syn, idx, nullptr,
                              -1.f, true, ts))) return rc;
-      launch_sub_inplace(lamT, hT, P_txt, ts);
+      if (!last) launch_sub_inplace(lamT, hT, P_txt, ts);
       if ((rc = img_backward(true, slot, tI[k], nuI, nullptr, xbar_t, hI, a->grad_image_syn, idx, nullptr,
                              -1.f, false, true, st))) return rc;
       if (a->use_lr_as_scale) launch_accum_f2d(dsc + 4, sbar_t, -1.0, st);
-      launch_sub_inplace(lamI, hI, P_img, st);
+      if (!last) launch_sub_inplace(lamI, hI, P_img, st);
     }
     join_from(ts, st);
     launch_d2f(a->grad_lr, dsc + 4, 1.f, 0, 2, st);
@@ -2041,6 +2100,9 @@ const char* mdd_last_error(void) { return g_err.c_str(); }
 int mdd_version(void) { return MDD_ABI_VERSION; }
 size_t mdd_sizeof_iter_args(void) { return sizeof(mdd_iter_args); }
 int mdd_set_se_fused(int enable) { return g_se_fused.exchange(enable != 0 ? 1 : 0, std::memory_order_relaxed); }
+int mdd_set_skip_unused_param_grads(int enable) {
+  return g_skip_unused.exchange(enable != 0 ? 1 : 0, std::memory_order_relaxed);
+}
 
 int mdd_engine_create(const mdd_config* cfg, mdd_engine** out) {
   CHECK_ARG(cfg && out && cfg->variant, "null config");

@@ -15,13 +15,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one(lib_path, dtype, steps, workload, own_stream=False):
+def one(lib_path, dtype, steps, workload, own_stream=False, keep_steps=None):
     import torch
     if own_stream:
         torch.cuda.set_stream(torch.cuda.Stream(priority=-1 if own_stream == "high" else 0))
     from multimodal_dataset_distillation_amd import _lib
     _lib.LIB_PATH = os.path.abspath(lib_path)
     os.environ.pop("MDD_HIP_LIB", None)
+    probe = C.CDLL(_lib.LIB_PATH)
+    for name in [s for s in _lib.SIGNATURES if not hasattr(probe, s)]:   # an older build (same ABI) without this symbol
+        del _lib.SIGNATURES[name]
     from multimodal_dataset_distillation_amd.engine import UnrollEngine
     from multimodal_dataset_distillation_amd.networks import (student_move_normalised_targets,
                                                                synthetic_expert_params)
@@ -32,12 +35,15 @@ def one(lib_path, dtype, steps, workload, own_stream=False):
                                  # clip: the reference's --image_encoder clip (ViT-B/32 tower) with CLIP's 512-d text embeddings
                                  "clip": ("clip_vit_b32", 100, 8, 224, 512)}[workload]
     dev = torch.device("cuda", 0)
-    eng = UnrollEngine(variant, batch=n, num_queries=n, image_size=size, d_txt=d_txt, syn_steps=K, dtype=dtype, device=dev)
+    eng = UnrollEngine(variant, batch=n, num_queries=n, image_size=size, d_txt=d_txt, syn_steps=K, dtype=dtype, device=dev,
+                       **({} if keep_steps is None else {"keep_steps": keep_steps}))
     lib = _lib.load()
     if os.environ.get("AB_NO_PIPE"):          # A/B of the 256 x 256 pipelined kernels inside one build
         lib.mdd_set_pipe_kernels(0)
     if os.environ.get("AB_SE_FUSED") is not None:   # A/B of the squeeze-excite apply in conv3's epilogue inside one build
         lib.mdd_set_se_fused(int(os.environ["AB_SE_FUSED"]))
+    if os.environ.get("AB_SKIP_UNUSED") is not None:   # A/B of the skipped parameter gradients of the unrolled match
+        lib.mdd_set_skip_unused_param_grads(int(os.environ["AB_SKIP_UNUSED"]))
     g = torch.Generator().manual_seed(0)
     image_syn = torch.randn(n, 3, size, size, generator=g).to(dev)
     text_syn = (torch.randn(n, d_txt, generator=g) * 0.5253).to(dev)
@@ -79,14 +85,17 @@ def main():
     ap.add_argument("--workload", default="c2", choices=["c2", "c1", "c5", "res", "reg", "clip"])
     ap.add_argument("--stream", nargs="?", const="normal", default=None, choices=["normal", "high"],
                     help="run on a non-default HIP stream; 'high' = a high-priority stream")
+    ap.add_argument("--keep-steps", type=int, default=None,
+                    help="activation sets kept (the engine's keep_steps; default: every step); 0 recomputes all but the last")
     ap.add_argument("libs", nargs="*")
     a = ap.parse_args()
     if a.one:
-        one(a.one, a.dtype, a.steps, a.workload, a.stream)
+        one(a.one, a.dtype, a.steps, a.workload, a.stream, a.keep_steps)
         return
     for lib in a.libs:
         rc = subprocess.call([sys.executable, os.path.abspath(__file__), "--one", lib, "--dtype", a.dtype,
-                              "--steps", str(a.steps), "--workload", a.workload] + (["--stream", a.stream] if a.stream else []))
+                              "--steps", str(a.steps), "--workload", a.workload] + (["--stream", a.stream] if a.stream else []) +
+                             ([] if a.keep_steps is None else ["--keep-steps", str(a.keep_steps)]))
         if rc:
             print("FAILED", lib, rc, flush=True)
 
